@@ -50,7 +50,23 @@ compared bit-exactly with the OpenMP CPU reference after the timed region
 (``verified_bit_exact``); the GPU/CPU speedup compares one GPU's per-image
 time with that CPU reference on the same 4096^2 image (``speedup_vs_cpu``).
 
-Run:  python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run does only what the headline needs: set-up, warm-up, the K timed
+steps over the rotated pairs, then the result line (``metric``, ``value``,
+``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step`` and the run's
+configuration). Everything else described above — the sustained, steady and
+cache-resident rates, the streaming phase, the clock sampler, the bit-exact
+verification against the CPU reference and the CPU baselines — runs only with
+``--full``.
+
+``--dump-outputs DIR`` writes what the last timed step computed: rank r's
+output slab of that step as ``DIR/out_rank<r>.npy`` (float32, rows x W x 4) —
+the whole slab when it fits the 64 MB budget shared by all ranks, else a
+fixed seeded choice of its rows (the slab's first and last two among them) —
+and the rows' indices within the slab as ``DIR/rows_rank<r>.npy`` (float64).
+The inputs are seeded, so two builds run with the same arguments can be
+compared output for output.
+
+Run:  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   With --gpus N > 1 and no torchrun environment, bench.py launches N ranks
   itself (torch.distributed.run, one process per GPU) before touching the GPU,
   and fails (exit 2) when fewer than N GPUs are visible. Under
@@ -139,7 +155,21 @@ def parse_args(argv=None):
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-verify", action="store_true")
     p.add_argument("--device", default="auto", choices=["auto", "cuda", "cpu"])
-    return p.parse_args(argv)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline's timed steps also run everything else this benchmark measures and "
+                        "checks: value_sustained, value_steady, value_warm_cache*, the streaming phase, --clocks, "
+                        "the bit-exact verification against the CPU reference and the CPU baselines (each still "
+                        "under its own option above). Without it only the headline is measured")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's output slab (or a fixed seeded choice of its rows; at most "
+                        "64 MB over all ranks) as DIR/out_rank<r>.npy, float32, with the rows' indices in "
+                        "DIR/rows_rank<r>.npy")
+    a = p.parse_args(argv)
+    if not a.full:  # a plain run: set-up, warm-up, the timed steps, the result line
+        a.sustain_ms = a.steady_ms = a.clocks = 0.0
+        a.stream = False
+        a.no_warm = a.no_cpu_baseline = a.no_verify = True
+    return a
 
 
 def main() -> int:
@@ -286,6 +316,8 @@ def run(args) -> int:
     enqueue_ms = issue_s[rot_step] * 1e3 / max(1, args.steps)
     watchdog.beat()
     elapsed = span.job_s  # the job's time: first rank's start to last rank's end
+    if args.dump_outputs:  # what the last timed step returned (pair (K - 1) % rotate)
+        dump_outputs(args.dump_outputs, dets[(args.steps - 1) % len(dets)].out, ctx)
 
     # the same K steps after >= sustain_ms of continuous load (the clock the
     # board holds under sustained load): reported beside `value`, not instead
@@ -479,7 +511,10 @@ def run(args) -> int:
             "distinct_devices": len(set(rank_devices)),
             "rehearsal": rehearsal,
             **span.fields(args.steps),
-            "verified_bit_exact": ok and (args.no_verify or checked == len(dets) * global_rows * args.size),
+            "full": args.full,
+            # a plain run compares nothing (null); --full: every pixel against the CPU reference
+            "verified_bit_exact": (ok and (args.no_verify or checked == len(dets) * global_rows * args.size)
+                                   if args.full else None),
             "verified_pixels": checked,
             "verified_one_device": one_device,
             "device": str(torch.cuda.get_device_name(ctx.device)) if ctx.device.type == "cuda" else "cpu",
@@ -634,6 +669,31 @@ def run_streaming(args, ctx, n, timed, watchdog, sync, ops, parallel) -> dict:
     if rec.get("verified_bit_exact") is None:
         rec.pop("verified_bit_exact", None)
     return rec
+
+
+DUMP_BYTES = 48 << 20  # float32 rows over all ranks; with the row indices well inside 64 MB
+
+
+def dump_outputs(path: str, out, ctx) -> None:
+    """--dump-outputs: this rank's output slab of the last timed step as
+    float32, whole when the ranks' slabs fit DUMP_BYTES together, else a fixed
+    seeded choice of its rows (always with the first and last two: the image
+    border and the halo rows' consumers), plus the chosen rows' indices."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    rows = out.shape[0]
+    keep = max(1, min(rows, DUMP_BYTES // ctx.world // (out[0].numel() * 4)))
+    idx = torch.arange(rows)
+    if keep < rows:
+        g = torch.Generator().manual_seed(4096 + ctx.rank)
+        edge = torch.tensor(sorted({0, 1, rows - 2, rows - 1} & set(range(rows))))
+        pick = torch.randperm(rows, generator=g)
+        idx = torch.cat([edge, pick[~torch.isin(pick, edge)]])[:keep].sort().values
+    vals = out.index_select(0, idx.to(out.device)).to("cpu").to(torch.float32)
+    np.save(os.path.join(path, f"out_rank{ctx.rank}.npy"), vals.numpy())
+    np.save(os.path.join(path, f"rows_rank{ctx.rank}.npy"), idx.to(torch.float64).numpy())
 
 
 def device_id(dev) -> str:

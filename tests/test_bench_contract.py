@@ -37,7 +37,7 @@ def _run(args, nproc=None, rc=0, env=None):
 
 
 def test_bench_contract_two_ranks_cpu():
-    rec = _run(["--gpus", "2", "--device", "cpu", "--size", "96", "--steps", "3", "--warmup", "1"], nproc=2)
+    rec = _run(["--gpus", "2", "--device", "cpu", "--size", "96", "--steps", "3", "--warmup", "1", "--full"], nproc=2)
     assert REQUIRED <= set(rec)
     assert rec["n_gpus"] == 2 and rec["steps"] == 3 and rec["warmup"] == 1 and rec["scaling"] == "weak"
     assert rec["higher_is_better"] is True and rec["value"] > 0 and rec["verified_bit_exact"] is True
@@ -68,7 +68,7 @@ def test_bench_measurement_hygiene_fields_cpu():
     published-methodology serial -O0 time rides along, and the time-based
     warm-up reports what it ran (the driver's "warmup" field stays W)."""
     rec = _run(["--device", "cpu", "--size", "64", "--steps", "2", "--warmup", "1", "--rotate", "2", "--no-stream",
-                "--warmup-ms", "5"])
+                "--warmup-ms", "5", "--full"])
     assert rec["warmup"] == 1 and rec["warmup_ms"] >= 5.0 and rec["warmup_steps_run"] >= 2
     # the sustained-load rate rides along (same K steps after >= sustain_ms of load)
     assert rec["value_sustained"] > 0 and rec["sustain_ms"] == 50.0
@@ -98,6 +98,75 @@ def test_bench_contract_single_process_cpu():
     assert REQUIRED <= set(rec) and rec["n_gpus"] == 1
 
 
+MOVED_BEHIND_FULL = {"value_sustained", "value_steady", "value_warm_cache", "value_warm_cache_1stream",
+                     "value_streaming", "cpu_ms_per_image", "speedup_vs_cpu", "clocks", "steady_clocks"}
+
+
+def test_bench_plain_run_measures_the_headline_only():
+    """A plain run (no --full) sets up, warms up, times the K steps and prints
+    the result line: none of the secondary measurements, no comparison with
+    the CPU reference (verified_bit_exact null), whatever their own options
+    say; --full brings them back."""
+    args = ["--device", "cpu", "--size", "64", "--steps", "4", "--warmup", "1", "--rotate", "2", "--clocks", "50"]
+    rec = _run(args)
+    assert REQUIRED <= set(rec) and rec["full"] is False and rec["status"] == "ok"
+    assert not MOVED_BEHIND_FULL & set(rec), MOVED_BEHIND_FULL & set(rec)
+    assert rec["verified_bit_exact"] is None and rec["verified_pixels"] == 0
+    assert rec["steps"] == 4 and rec["ms_per_step"] > 0 and rec["dtype"] == "fp32" and rec["unit"] == "Gpixel/s"
+    assert abs(rec["ms_per_step"] * 4 - rec["job_span_ms"]) <= 1e-3 * rec["job_span_ms"] + 1e-4
+    full = _run(args + ["--full"])
+    assert full["full"] is True and full["verified_bit_exact"] is True and full["verified_pixels"] == 2 * 64 * 64
+    # (on the CPU: no clock sampler, and one stream, whose cache-resident rate is value_warm_cache)
+    assert MOVED_BEHIND_FULL - {"clocks", "steady_clocks", "value_warm_cache_1stream"} <= set(full)
+
+
+def test_bench_dump_outputs_cpu(tmp_path):
+    """--dump-outputs: the last timed step's output slab as float32, the same
+    from run to run (seeded inputs), and equal to the CPU reference on the
+    regenerated input of the pair that step used."""
+    import numpy as np
+    import torch
+
+    import bench
+    from cuda_mpi_openmp_amd import ops
+
+    args = ["--device", "cpu", "--size", "67", "--steps", "4", "--warmup", "1", "--rotate", "3"]
+    a, b = tmp_path / "a", tmp_path / "b"
+    _run(args + ["--dump-outputs", str(a)])
+    _run(args + ["--dump-outputs", str(b), "--full"])
+    assert sorted(os.listdir(a)) == sorted(os.listdir(b)) == ["out_rank0.npy", "rows_rank0.npy"]
+    out, rows = np.load(a / "out_rank0.npy"), np.load(a / "rows_rank0.npy")
+    assert out.dtype == np.float32 and out.shape == (67, 67, 4) and rows.dtype == np.float64
+    assert np.array_equal(rows, np.arange(67)) and np.array_equal(out, np.load(b / "out_rank0.npy"))
+    img = bench.regen_slab(1234 + 7919 * ((4 - 1) % 3), 67, 67, torch.device("cpu"))  # the last step's pair
+    assert np.array_equal(out, ops.conv(img, "sobel5").numpy().astype(np.float32))
+
+
+def test_bench_dump_outputs_samples_rows_of_a_large_slab(tmp_path, monkeypatch):
+    """A slab above the size budget is written as a fixed seeded choice of its
+    rows: sorted, distinct, with the first and last two, the same every time,
+    within the budget, and the ranks share the budget."""
+    import argparse
+
+    import numpy as np
+    import torch
+
+    import bench
+
+    out = bench.regen_slab(5, 40, 8, torch.device("cpu"))
+    monkeypatch.setattr(bench, "DUMP_BYTES", 20 * 8 * 4 * 4)  # 20 rows of float32
+    for world, keep in ((1, 20), (2, 10)):
+        ctx = argparse.Namespace(world=world, rank=world - 1)
+        for d in ("x", "y"):
+            bench.dump_outputs(str(tmp_path / f"{d}{world}"), out, ctx)
+        rows = np.load(tmp_path / f"x{world}" / f"rows_rank{world - 1}.npy")
+        vals = np.load(tmp_path / f"x{world}" / f"out_rank{world - 1}.npy")
+        assert len(rows) == keep and list(rows) == sorted(set(rows)) and {0, 1, 38, 39} <= set(rows)
+        assert vals.dtype == np.float32 and vals.nbytes <= bench.DUMP_BYTES // world
+        assert np.array_equal(vals, out.numpy()[rows.astype(int)].astype(np.float32))
+        assert np.array_equal(rows, np.load(tmp_path / f"y{world}" / f"rows_rank{world - 1}.npy"))
+
+
 def test_bench_jacobi_two_ranks_cpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
            "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "tools", "bench_jacobi.py"), "--device", "cpu",
@@ -124,7 +193,8 @@ def test_bench_jacobi_catches_injected_halo_corruption():
 
 def test_bench_self_launches_ranks_cpu():
     """--gpus N without a torchrun environment launches N ranks itself."""
-    rec = _run(["--gpus", "3", "--device", "cpu", "--size", "64", "--steps", "2", "--warmup", "1", "--rotate", "2"])
+    rec = _run(["--gpus", "3", "--device", "cpu", "--size", "64", "--steps", "2", "--warmup", "1", "--rotate", "2",
+                "--full"])
     assert rec["n_gpus"] == 3 and rec["world_size_seen"]["torch_distributed"] == 3
     # one entry per rank naming the device it ran on (PCI location on GPUs)
     assert rec["rank_devices"] == ["cpu"] * 3 and rec["distinct_devices"] == 1
@@ -188,7 +258,8 @@ def test_bench_value_is_job_span_with_start_skew():
 
 def test_scale_driver_job_is_the_driver_command():
     """SCALE N = 1 equals BENCH: tools/scale.py's conv/driver job runs exactly
-    the driver's bench.py --gpus N --steps K --warmup W."""
+    the driver's bench.py --gpus N --steps K --warmup W, plus --full (the
+    headline first, then the streaming curve and the verification)."""
     import argparse
     import importlib.util
 
@@ -199,7 +270,7 @@ def test_scale_driver_job_is_the_driver_command():
                            driver_warmup=5)
     for n in (1, 2, 8):
         job = [j for j in scale.plan(n, a, 8) if j["name"] == "conv/driver"][0]
-        assert job["cmd"][1:] == ["bench.py", "--gpus", str(n), "--steps", "20", "--warmup", "5"]
+        assert job["cmd"][1:] == ["bench.py", "--gpus", str(n), "--steps", "20", "--warmup", "5", "--full"]
         assert job["skip"] is None
 
 
@@ -211,7 +282,7 @@ def test_bench_streaming_timeout_on_one_rank_cpu():
     record's status says streaming_failed; --strict-streaming turns it into a
     non-zero exit."""
     args = ["--gpus", "2", "--device", "cpu", "--size", "64", "--steps", "2", "--warmup", "1", "--rotate", "2",
-            "--no-warm", "--sustain-ms", "0", "--no-cpu-baseline"]
+            "--no-warm", "--sustain-ms", "0", "--no-cpu-baseline", "--full"]
     rec = _run(args, nproc=2, env={"MPX_BENCH_INJECT_STREAM_TIMEOUT": "1"})
     assert rec["value"] > 0 and rec["verified_bit_exact"] is True and rec["verified_pixels"] == 2 * 2 * 64 * 64
     assert rec["value_streaming"] is None and "timed out" in rec["streaming_error"]
@@ -236,7 +307,8 @@ def test_bench_strong_layout_equals_one_device_cpu():
     the record says strong."""
     for n in (2, 3):
         rec = _run(["--gpus", str(n), "--device", "cpu", "--layout", "strong", "--size", "97", "--steps", "2",
-                    "--warmup", "1", "--rotate", "2", "--no-warm", "--sustain-ms", "0", "--no-cpu-baseline"], nproc=n)
+                    "--warmup", "1", "--rotate", "2", "--no-warm", "--sustain-ms", "0", "--no-cpu-baseline", "--full"],
+                   nproc=n)
         assert rec["scaling"] == "strong" and rec["config"]["layout"] == "strong"
         assert rec["config"]["image_hw"] == [97, 97] and sum(rec["config"]["rows_per_rank"]) == 97
         assert rec["verified_one_device"] is True and rec["verified_bit_exact"] is True
@@ -244,7 +316,7 @@ def test_bench_strong_layout_equals_one_device_cpu():
         # value: the ONE image's pixels per step over the job span
         assert abs(rec["value"] - 97 * 97 / (rec["ms_per_step"] * 1e-3) / 1e9) < 1e-3 * max(1e-3, rec["value"])
     one = _run(["--device", "cpu", "--layout", "strong", "--size", "64", "--steps", "2", "--warmup", "1",
-                "--rotate", "2", "--no-stream", "--no-warm", "--sustain-ms", "0", "--no-cpu-baseline"])
+                "--rotate", "2", "--no-stream", "--no-warm", "--sustain-ms", "0", "--no-cpu-baseline", "--full"])
     assert one["n_gpus"] == 1 and one["config"]["image_hw"] == [64, 64] and one["verified_one_device"] is True
 
 

@@ -51,7 +51,7 @@ def test_contract_bench_two_ranks_cpu():
     """The nccl branches (device scalars, object collectives, RCCL-halo p2p via
     batch_isend_irecv) run under the contract and give the gloo results."""
     args = ["--gpus", "2", "--device", "cpu", "--size", "64", "--steps", "3", "--warmup", "1", "--rotate", "2",
-            "--halo", "rccl", "--warmup-ms", "0"]
+            "--halo", "rccl", "--warmup-ms", "0", "--full"]
     rec = _rec(_bench(args, {"MPX_DIST_CONTRACT": "nccl"}))
     assert rec["n_gpus"] == 2 and rec["verified_bit_exact"] is True and rec["verified_bit_exact_streaming"] is True
     assert rec["rehearsal"] is True
@@ -74,7 +74,7 @@ def test_contract_bench_gpu(world):
     env = {"MPX_DIST_CONTRACT": "nccl", "HSA_ENABLE_IPC_MODE_LEGACY": "0"}
     for halo in ("auto", "rccl"):
         rec = _rec(_bench(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--rotate", "2", "--halo", halo,
-                           "--no-cpu-baseline", "--warmup-ms", "0"], env, nproc=world))
+                           "--no-cpu-baseline", "--warmup-ms", "0", "--full"], env, nproc=world))
         assert rec["n_gpus"] == world and rec["verified_bit_exact"] is True
         assert rec["verified_bit_exact_streaming"] is True and rec["rehearsal"] is True
 

@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 def test_bench_self_launch_two_ranks_peer(gpu):
     env = dict(os.environ, MPX_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--rotate", "2", "--size", "512", "--no-cpu-baseline", "--halo", "peer"],
+                        "--rotate", "2", "--size", "512", "--no-cpu-baseline", "--halo", "peer", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-2000:]
     rec = json.loads(r.stdout.strip().splitlines()[-1])
@@ -45,7 +45,7 @@ def test_bench_two_ranks_peer_map_failure_falls_back_everywhere(gpu):
     the static AND the streaming phase, every pixel still verified, rc 0."""
     env = dict(os.environ, MPX_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", MPX_PEER_INJECT="map_fail@1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--rotate", "2", "--size", "512", "--no-cpu-baseline", "--steady-ms", "0"],
+                        "--rotate", "2", "--size", "512", "--no-cpu-baseline", "--steady-ms", "0", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-2000:]
     rec = json.loads(r.stdout.strip().splitlines()[-1])
@@ -65,7 +65,7 @@ def test_bench_two_ranks_streaming_timeout_is_recorded(gpu):
     self-launch's torch.distributed.run reports that as 1)."""
     env = dict(os.environ, MPX_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", MPX_BENCH_INJECT_STREAM_TIMEOUT="1")
     args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-            "--rotate", "2", "--size", "512", "--no-cpu-baseline", "--steady-ms", "0"]
+            "--rotate", "2", "--size", "512", "--no-cpu-baseline", "--steady-ms", "0", "--full"]
     for strict in (False, True):
         r = subprocess.run(args + (["--strict-streaming"] if strict else []), cwd=ROOT, env=env,
                            capture_output=True, text=True, timeout=110)

@@ -100,7 +100,7 @@ case "$cmd" in
     # no name: tests + smoke + bench; NAME: the function ckpt_NAME of the
     # checkpoint table (tools/checkpoints/*.sh: r5.sh this round, r4_archive.sh)
     if [ $# -eq 0 ]; then
-      bash "$0" tests && bash "$0" smoke && bash "$0" bench
+      bash "$0" tests && bash "$0" smoke && bash "$0" bench --full
     else
       here=$(dirname "$0")
       for f in "$here"/checkpoints/*.sh; do . "$f"; done

@@ -23,7 +23,10 @@ the ideal lines). Efficiency: weak = value_N / (N * value_1); strong =
 t_1 / (N * t_N); every rate comes from the job span max(t_end) - min(t_start)
 (parallel/timing.py), and ``efficiency_max_rank`` shows the same ratio on the
 slowest rank's own span. ``conv/driver`` is the round-end driver's exact
-``bench.py --gpus N --steps K --warmup W``, so its N = 1 point equals BENCH. Runs that cannot execute here (fewer devices than N, RCCL
+``bench.py --gpus N --steps K --warmup W`` plus ``--full`` (the headline is
+measured first, as in a plain run), so its N = 1 point equals BENCH. Every
+bench.py job runs with ``--full``: the streaming curve and the ``verified``
+column come from it. Runs that cannot execute here (fewer devices than N, RCCL
 with several ranks on one GPU) are recorded as skipped with the reason.
 
 ``--rehearse``: several ranks share the GPUs (gloo control plane, peer halos
@@ -98,7 +101,8 @@ def plan(n: int, a, ndev: int) -> List[dict]:
     # the driver's own command (BENCH at N = 1, SCALE at every N): bench.py with
     # exactly --gpus N --steps K --warmup W, so this curve's N = 1 point is the
     # BENCH number (VERDICT r4 Next #1)
-    drv = [py, "bench.py", "--gpus", str(n), "--steps", str(a.driver_steps), "--warmup", str(a.driver_warmup)]
+    # (--full: the streaming curve and the verification come from the same run)
+    drv = [py, "bench.py", "--gpus", str(n), "--steps", str(a.driver_steps), "--warmup", str(a.driver_warmup), "--full"]
     if not cpu:
         assert drv[1:] == driver_command(n, a.driver_steps, a.driver_warmup), drv
     jobs.append({"name": "conv/driver", "kind": "weak", "skip": lacks,
@@ -108,7 +112,7 @@ def plan(n: int, a, ndev: int) -> List[dict]:
     # by the default transport; efficiency t_1 / (N t_N)
     jobs.append({"name": "conv/strong", "kind": "strong", "skip": lacks,
                  "cmd": [py, "bench.py", "--gpus", str(n), "--layout", "strong", "--steps", str(a.driver_steps),
-                         "--warmup", str(a.driver_warmup), "--no-cpu-baseline"]
+                         "--warmup", str(a.driver_warmup), "--no-cpu-baseline", "--full"]
                  + (dev + ["--size", "128", "--rotate", "2"] if cpu else [])})
     for halo in ("peer", "rccl"):
         skip = lacks
@@ -119,7 +123,8 @@ def plan(n: int, a, ndev: int) -> List[dict]:
         if cpu and halo == "peer" and n > 1:  # (also under --contract)
             skip = "peer halos need GPUs (IPC); the CPU run uses gloo send/recv"
         jobs.append({"name": f"conv/{halo}", "kind": "weak", "skip": skip,
-                     "cmd": [py, "bench.py", "--gpus", str(n), "--halo", halo, "--no-cpu-baseline", *dev, *conv_sz]})
+                     "cmd": [py, "bench.py", "--gpus", str(n), "--halo", halo, "--no-cpu-baseline", "--full", *dev,
+                             *conv_sz]})
         jobs.append({"name": f"jacobi/{halo}", "kind": "strong",
                      "skip": skip,
                      "cmd": [py, "tools/bench_jacobi.py", "--gpus", str(n), "--halo", halo, *dev, *jac_sz]})
@@ -148,8 +153,8 @@ def plan(n: int, a, ndev: int) -> List[dict]:
 
 
 def driver_command(n: int, steps: int, warmup: int) -> List[str]:
-    """The round-end driver's bench invocation (task contract), argv after the interpreter."""
-    return ["bench.py", "--gpus", str(n), "--steps", str(steps), "--warmup", str(warmup)]
+    """The round-end driver's bench invocation (task contract) with --full, argv after the interpreter."""
+    return ["bench.py", "--gpus", str(n), "--steps", str(steps), "--warmup", str(warmup), "--full"]
 
 
 def value_of(rec: dict) -> Optional[float]:
