@@ -104,6 +104,9 @@ _SIGNATURES = {
     "mpx_sort_ws_status": (c_int, [c_vp, c_i64, c_int]),
     "mpx_sort_lane_order_ok": (c_int, [c_vp]),
     "mpx_cpu_sort": (None, [c_vp, c_i64, c_int]),
+    "mpx_sort_pairs_workspace_bytes": (c_i64, [c_i64, c_int]),
+    "mpx_sort_pairs_ws": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp]),
+    "mpx_cpu_sort_pairs": (None, [c_vp, c_vp, c_i64, c_int, c_int]),
     "mpx_rows_checksum": (c_int, [c_vp, c_i64, c_int, c_i64, c_int, c_vp, c_vp]),
     "mpx_peer_probe_run": (c_int, [c_vp, c_vp]),
     "mpx_halo_fetch_run": (c_int, [c_vp, c_vp]),
@@ -128,6 +131,7 @@ _TUNE_SIGNATURES = {
     # lab5 radix variants / scatter probe (native/tune/sort_variants.hip)
     "mpx_sort_variant": (c_int, [c_vp, c_i64, c_int, c_vp, c_i64, c_int, c_vp]),
     "mpx_sort_scatter_probe": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp]),
+    "mpx_sort_pairs_variant": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_int, c_vp]),
     # lab1 / Jacobi tuning variants (native/tune/{vsub,jacobi}_variants.hip)
     "mpx_vsub_variant": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp]),
     "mpx_jacobi_variant": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp]),

@@ -5,7 +5,7 @@ from .classify import class_stats, classify_
 from .classify import plan as classify_plan
 from .edge import ConvLauncher, conv, conv_rows, roberts, roberts_rgb
 from .filters import Filter, get_filter, list_filters
-from .sort import sort_
+from .sort import argsort, sort, sort_, sort_pairs_
 from .stencil import jacobi_sweep
 from .vector import vsub
 
@@ -22,6 +22,9 @@ __all__ = [
     "get_filter",
     "list_filters",
     "jacobi_sweep",
+    "argsort",
+    "sort",
     "sort_",
+    "sort_pairs_",
     "vsub",
 ]

@@ -325,6 +325,25 @@ int mpx_sort(void *data, int64_t n, int dtype, void *stream);
  * ranking unless 1. */
 int mpx_sort_lane_order_ok(void *stream);
 
+/* Stable key-value sort, in place on the device: `keys` (int32 or float32,
+ * dtype MPX_SORT_I32 / MPX_SORT_F32, floats in the IEEE total order above) and
+ * one opaque 32-bit word per key in `vals`, moved with its key and never
+ * interpreted. Equal keys keep their input order, ascending and descending
+ * (as torch.sort(stable=True, descending=True)). Four 8-bit LSD radix passes
+ * for every n >= 2; n < 2^30 (MPX_ERR_UNSUPPORTED beyond, before any pointer
+ * is touched), MPX_SORT_U8 and unknown flag bits are MPX_ERR_UNSUPPORTED.
+ * flags: MPX_SORT_IOTA — `vals` is output only and receives the permutation
+ * (vals[i] = input index of the key now at i; the argsort), generated in the
+ * first pass instead of loaded; MPX_SORT_DESCENDING — descending keys.
+ * The workspace follows mpx_sort_ws: caller-provided,
+ * >= mpx_sort_pairs_workspace_bytes(n, dtype) bytes (a second n x 4 byte array
+ * beside the keys-only layout; 0 for n < 2), 16-byte aligned, stream-ordered.
+ * mpx_cpu_sort_pairs is the stable CPU reference (n < 2^32). */
+enum { MPX_SORT_IOTA = 1, MPX_SORT_DESCENDING = 2 };
+int64_t mpx_sort_pairs_workspace_bytes(int64_t n, int dtype);
+int mpx_sort_pairs_ws(void *keys, uint32_t *vals, int64_t n, int dtype, int flags, void *workspace,
+                      int64_t workspace_bytes, void *stream);
+
 /* ---------------- CPU references (OpenMP, -O3, same numerics) ---------------- */
 int mpx_cpu_threads(void);
 void mpx_cpu_vsub_f64(const double *a, const double *b, double *c, int64_t n);
@@ -336,6 +355,7 @@ void mpx_cpu_conv(const uint32_t *in, uint32_t *out, int w, int pitch, int oy0, 
 void mpx_cpu_classify(uint32_t *img, int64_t npix, int nc, const double *mu, const double *inv);
 double mpx_cpu_jacobi_f64(const double *u, double *un, int cols, int pitch, int r0, int r1);
 void mpx_cpu_sort(void *data, int64_t n, int dtype);
+void mpx_cpu_sort_pairs(void *keys, uint32_t *vals, int64_t n, int dtype, int flags);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,13 @@ extern "C" {
 int mpx_sort_variant(void *data, int64_t n, int dtype, void *workspace, int64_t workspace_bytes, int variant,
                      void *stream);
 
+/* mpx_sort_pairs_ws (capi.h) with a fixed production ranking form and tile
+ * size: 0 = AUTO, 7 / 8 the peer-mask fallback (8192 / 4096-key tiles),
+ * 20 / 21 / 22 the returning-add ranking with hot digits (8192 / 4096 /
+ * 16384-key tiles). Any other variant is refused. */
+int mpx_sort_pairs_variant(void *keys, uint32_t *vals, int64_t n, int dtype, int flags, void *workspace,
+                           int64_t workspace_bytes, int variant, void *stream);
+
 /* Count + scan + lean scatter for each digit of the unchanged keys with step
  * knock-outs (radix_scatter_lean_kernel KNOCK: 0, 1, 6, 12, 14, 16, 31); the
  * workspace holds garbage afterwards, `data` is not modified. */

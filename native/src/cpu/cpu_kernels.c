@@ -546,3 +546,95 @@ void mpx_cpu_sort(void *data, int64_t n, int dtype) {
         x[i] = is_float ? (k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)) : (k ^ 0x80000000u);
     }
 }
+
+/* ---- stable key-value sort: 64-bit composites (order-preserving key << 32 |
+ * input index). The index makes every composite distinct, so any sort of the
+ * composites is the stable sort of the keys (qsort alone is not stable);
+ * descending complements the key, which keeps equal keys in input order. ---- */
+static int cmp_u64(const void *a, const void *b) {
+    const uint64_t x = *(const uint64_t *)a, y = *(const uint64_t *)b;
+    return (x > y) - (x < y);
+}
+
+#ifdef _OPENMP
+static void merge_u64(const uint64_t *a, int64_t na, const uint64_t *b, int64_t nb, uint64_t *out) {
+    int64_t i = 0, j = 0, o = 0;
+    while (i < na && j < nb) out[o++] = b[j] < a[i] ? b[j++] : a[i++];
+    while (i < na) out[o++] = a[i++];
+    while (j < nb) out[o++] = b[j++];
+}
+
+/* sort_u32_parallel on composites: sorted runs, then rounds of pairwise
+ * merges; the result is in x or tmp (returned), NULL = not taken */
+static uint64_t *sort_u64_parallel(uint64_t *x, uint64_t *tmp, int64_t n) {
+    int runs = omp_get_max_threads();
+    if (runs < 2 || n < (1 << 16)) return NULL;
+    int64_t *bound = (int64_t *)malloc((size_t)(runs + 1) * sizeof(int64_t));
+    if (!bound) return NULL;
+    for (int r = 0; r <= runs; ++r) bound[r] = n * r / runs;
+#pragma omp parallel for schedule(static)
+    for (int r = 0; r < runs; ++r) qsort(x + bound[r], (size_t)(bound[r + 1] - bound[r]), sizeof(uint64_t), cmp_u64);
+    uint64_t *src = x, *dst = tmp;
+    for (int width = 1; width < runs; width *= 2) {
+#pragma omp parallel for schedule(dynamic, 1)
+        for (int r = 0; r < runs; r += 2 * width) {
+            const int mid = r + width < runs ? r + width : runs;
+            const int end = r + 2 * width < runs ? r + 2 * width : runs;
+            merge_u64(src + bound[r], bound[mid] - bound[r], src + bound[mid], bound[end] - bound[mid], dst + bound[r]);
+        }
+        uint64_t *t = src;
+        src = dst;
+        dst = t;
+    }
+    free(bound);
+    return src;
+}
+#endif
+
+void mpx_cpu_sort_pairs(void *keys, uint32_t *vals, int64_t n, int dtype, int flags) {
+    const int iota = flags & 1, desc = flags & 2; /* MPX_SORT_IOTA, MPX_SORT_DESCENDING */
+    if (n < 1 || n > (int64_t)0xffffffff || (dtype != MPX_SORT_I32 && dtype != MPX_SORT_F32)) return;
+    if (n == 1) {
+        if (iota) vals[0] = 0;
+        return;
+    }
+    uint32_t *x = (uint32_t *)keys;
+    const int is_float = dtype == MPX_SORT_F32;
+    const uint32_t flip = desc ? 0xffffffffu : 0u;
+    /* composites, a merge buffer, and the caller's payload (gathered from) */
+    uint64_t *c = (uint64_t *)malloc((size_t)n * sizeof(uint64_t));
+    uint64_t *tmp = (uint64_t *)malloc((size_t)n * sizeof(uint64_t));
+    uint32_t *pay = iota ? NULL : (uint32_t *)malloc((size_t)n * sizeof(uint32_t));
+    if (!c || !tmp || (!iota && !pay)) {
+        fprintf(stderr, "mpx_cpu_sort_pairs: out of memory for %lld pairs\n", (long long)n);
+        abort();
+    }
+    if (pay) memcpy(pay, vals, (size_t)n * sizeof(uint32_t));
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static)
+#endif
+    for (int64_t i = 0; i < n; ++i) {
+        const uint32_t v = x[i];
+        const uint32_t k = is_float ? (v ^ ((uint32_t)((int32_t)v >> 31) | 0x80000000u)) : (v ^ 0x80000000u);
+        c[i] = ((uint64_t)(k ^ flip) << 32) | (uint64_t)i;
+    }
+    uint64_t *sorted = NULL;
+#ifdef _OPENMP
+    sorted = sort_u64_parallel(c, tmp, n);
+#endif
+    if (!sorted) {
+        qsort(c, (size_t)n, sizeof(uint64_t), cmp_u64);
+        sorted = c;
+    }
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static)
+#endif
+    for (int64_t i = 0; i < n; ++i) {
+        const uint32_t k = (uint32_t)(sorted[i] >> 32) ^ flip, idx = (uint32_t)sorted[i];
+        x[i] = is_float ? (k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)) : (k ^ 0x80000000u);
+        vals[i] = iota ? idx : pay[idx];
+    }
+    free(c);
+    free(tmp);
+    free(pay);
+}

@@ -29,6 +29,9 @@ void mpx_cpu_classify(uint32_t *img, int64_t npix, int nc, const double *mu, con
 double mpx_cpu_jacobi_f64(const double *u, double *un, int cols, int pitch, int r0, int r1);
 /* lab5: ascending sort in place, same order as mpx_sort (dtype: enum mpx_sort_dtype). */
 void mpx_cpu_sort(void *data, int64_t n, int dtype);
+/* Stable key-value sort, same order and flags as mpx_sort_pairs_ws (capi.h:
+ * 1 = MPX_SORT_IOTA, 2 = MPX_SORT_DESCENDING); int32 / float32 keys, n < 2^32. */
+void mpx_cpu_sort_pairs(void *keys, uint32_t *vals, int64_t n, int dtype, int flags);
 
 /* lab1 host text I/O (reference lab1/src/main.cu:46-52 scanf per value,
  * :82-84 printf per value), parallel over OpenMP threads in the -fopenmp builds

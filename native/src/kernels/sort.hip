@@ -35,6 +35,10 @@
 //     every block scans the 256 counts itself and writes one contiguous run of
 //     16-B pieces of the output, a piece's value searched only among the
 //     buckets its run overlaps (fill_u8_kernel).
+//   * Key-value pairs and argsort (mpx_sort_pairs_ws, radix_sort_pairs32
+//     below): the same passes with the payload-carrying scatter of
+//     sort_pairs.hpp; stable, ascending or descending, every n < 2^30 on the
+//     radix path (the bitonic networks are not stable).
 //   * Scratch comes from a caller-provided workspace (mpx_sort_workspace_bytes
 //     / mpx_sort_ws): the Python op takes it from torch's caching allocator on
 //     the tensor's stream, so concurrent sorts on different streams or devices
@@ -44,6 +48,7 @@
 #include <type_traits>
 
 #include "mpx/tuning.h"
+#include "sort_pairs.hpp"
 #include "sort_radix.hpp"
 
 namespace mpx {
@@ -427,6 +432,77 @@ int radix_sort32(uint32_t *x, int64_t n, int mode, void *ws, int variant, hipStr
     return MPX_OK;
 }
 
+// Key-value form of radix_sort32 (mpx_sort_pairs_ws): the same count and scan
+// kernels, the pairs scatter of sort_pairs.hpp, keys and payload ping-ponging
+// data -> workspace -> data. `vtmp` is the payload's half of the workspace.
+// AUTO: 4096-key tiles up to kTile4kMaxN keys — the keys-only threshold,
+// inherited (at 2^23 pairs the 8192-key form measured 2-3 % ahead, inside what
+// one box's runs decide) — and 16384-key tiles from kPairsTile16kMinN = 2^25,
+// measured for pairs (2^25 int32 / float32 argsort: 0.527 / 0.540 ms against
+// 0.563 / 0.554 on 8192-key tiles, two runs; 2^24: 0.289 against 0.277;
+// profiles/lab5_sort.md). The peer-mask fallback's blocks hold 45 / 89 KiB of
+// LDS (tables + two staging arrays), so 3 / 1 of them fit a CU where
+// keys-only runs 4 / 2.
+constexpr int64_t kPairsTile16kMinN = (int64_t)1 << 25;
+
+int radix_sort_pairs32(uint32_t *x, uint32_t *vals, int64_t n, int mode, int flags, void *ws, int variant,
+                       hipStream_t s) {
+    const RadixWs r = radix_layout(ws, n);
+    uint32_t *vtmp = reinterpret_cast<uint32_t *>(static_cast<char *>(ws) + radix_ws_bytes(n));
+    const bool auto_variant = variant == 0;
+    if (variant == 0) variant = n <= kTile4kMaxN ? 21 : n < kPairsTile16kMinN ? 20 : 22;
+    if (variant != 7 && variant != 8 && (variant < 20 || variant > 22)) return MPX_ERR_UNSUPPORTED;
+    // as radix_sort32: the returning-add ranking needs ascending lane order
+    if (variant >= 20 && lds_rtn_order_ok(s) != 1) {
+        if (!auto_variant) return MPX_ERR_UNSUPPORTED;
+        variant = n <= kTile4kMaxN ? 8 : 7;
+    }
+    const bool small_tiles = variant == 8 || variant == 21;
+    const bool big_tiles = variant == 22;
+    const int ntiles = small_tiles ? (int)((n + kRTileSmall - 1) / kRTileSmall)
+                       : big_tiles ? (int)((n + kRTileBig - 1) / kRTileBig)
+                                   : (int)r.tiles;
+    const bool iota = (flags & MPX_SORT_IOTA) != 0;
+    const uint32_t flip = (flags & MPX_SORT_DESCENDING) ? 0xffffffffu : 0u;
+    MPX_RETURN_IF_HIP_ERROR(hipMemsetAsync(r.err, 0, sizeof(uint32_t), s));
+    for (int p = 0; p < 4; ++p) {
+        const uint32_t *src = (p & 1) ? r.tmp : x, *vsrc = (p & 1) ? vtmp : vals;
+        uint32_t *dst = (p & 1) ? x : r.tmp, *vdst = (p & 1) ? vals : vtmp;
+        const int in_mode = p == 0 ? mode : (int)kRawKeys;
+        // the digit counts of the ascending key; a descending pass 0 reads them mirrored
+        if (small_tiles)
+            hipLaunchKernelGGL(radix_count_kernel<kRTileSmall>, dim3((unsigned)ntiles), dim3(kCThreads), 0, s, src, n,
+                               8 * p, in_mode, r.status, ntiles);
+        else if (big_tiles)
+            hipLaunchKernelGGL(radix_count_kernel<kRTileBig>, dim3((unsigned)ntiles), dim3(kCThreads), 0, s, src, n,
+                               8 * p, in_mode, r.status, ntiles);
+        else
+            hipLaunchKernelGGL(radix_count_kernel<kRTile>, dim3((unsigned)ntiles), dim3(kCThreads), 0, s, src, n,
+                               8 * p, in_mode, r.status, ntiles);
+        MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
+        hipLaunchKernelGGL(radix_scan1024_kernel, dim3(256), dim3(kScanThreads), 0, s, r.status, ntiles, r.hist);
+        MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
+        const int rounded = (ntiles + kNumXCDs - 1) / kNumXCDs * kNumXCDs;
+        if (variant == 7)
+            launch_pairs<kRThreads, 0>(p, mode, iota, flip, std::min(kNumCUs, rounded), s, src, dst, vsrc, vdst, n,
+                                          r.hist, r.status, ntiles);
+        else if (variant == 8)
+            launch_pairs<kRThreads / 2, 0>(p, mode, iota, flip, std::min(kNumCUs * 3, rounded), s, src, dst, vsrc,
+                                              vdst, n, r.hist, r.status, ntiles);
+        else if (variant == 20)
+            launch_pairs<kRThreads, 4>(p, mode, iota, flip, std::min(kNumCUs * 2, rounded), s, src, dst, vsrc, vdst,
+                                          n, r.hist, r.status, ntiles);
+        else if (variant == 21)
+            launch_pairs<kRThreads / 2, 4>(p, mode, iota, flip, std::min(kNumCUs * 4, rounded), s, src, dst, vsrc,
+                                              vdst, n, r.hist, r.status, ntiles);
+        else
+            launch_pairs<kRThreads * 2, 4>(p, mode, iota, flip, std::min(kNumCUs, rounded), s, src, dst, vsrc, vdst,
+                                              n, r.hist, r.status, ntiles);
+        MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
+    }
+    return MPX_OK;
+}
+
 int grid_for(int64_t work, int block) {
     return (int)std::max<int64_t>(1, std::min<int64_t>((work + block - 1) / block, (int64_t)kNumCUs * 16));
 }
@@ -518,6 +594,52 @@ int sort_impl(void *data, int64_t n, int dtype, void *ws, int64_t ws_bytes, void
     return MPX_OK;
 }
 
+// n >= 2^30 is refused (30-bit radix counts, 32-bit payload index); every
+// smaller n >= 2 takes the radix path, n <= 4096 included: the one-launch
+// bitonic network is not stable, and one stable code path for every size is
+// worth more here than the launches a 64-bit composite network would save.
+int64_t sort_pairs_workspace_bytes(int64_t n, int dtype) {
+    if (n < 2 || n >= kRadixMaxN || (dtype != MPX_SORT_I32 && dtype != MPX_SORT_F32)) return 0;
+    return (int64_t)radix_pairs_ws_bytes(n);
+}
+
+int sort_pairs_impl(void *keys, uint32_t *vals, int64_t n, int dtype, int flags, void *ws, int64_t ws_bytes,
+                    void *stream, int variant) {
+    MPX_CHECK_ARG(n >= 0, "n must be >= 0");
+    if (dtype != MPX_SORT_I32 && dtype != MPX_SORT_F32) {
+        set_error("sort_pairs: keys are int32 or float32 (dtype %d)", dtype);
+        return MPX_ERR_UNSUPPORTED;
+    }
+    if (flags & ~(MPX_SORT_IOTA | MPX_SORT_DESCENDING)) {
+        set_error("sort_pairs: unknown flag bits 0x%x", (unsigned)flags);
+        return MPX_ERR_UNSUPPORTED;
+    }
+    if (n >= kRadixMaxN) {
+        set_error("sort_pairs: n = %lld is beyond the 30-bit radix counts (n < 2^30)", (long long)n);
+        return MPX_ERR_UNSUPPORTED;
+    }
+    if (variant != 0 && variant != 7 && variant != 8 && (variant < 20 || variant > 22)) {
+        set_error("sort_pairs variant %d: 0 (auto), 7, 8, 20, 21, 22", variant);
+        return MPX_ERR_ARG;
+    }
+    hipStream_t s = as_stream(stream);
+    if (n == 0) return MPX_OK;
+    MPX_CHECK_ARG(keys && vals, "null keys or values");
+    MPX_CHECK_ARG(((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(vals)) & 3u) == 0,
+                  "keys and values must be 4-byte aligned");
+    if (n == 1) {
+        if (flags & MPX_SORT_IOTA) MPX_RETURN_IF_HIP_ERROR(hipMemsetAsync(vals, 0, sizeof(uint32_t), s));  // index 0
+        return MPX_OK;
+    }
+    MPX_CHECK_ARG(ws && ws_bytes >= sort_pairs_workspace_bytes(n, dtype),
+                  "workspace smaller than mpx_sort_pairs_workspace_bytes(n, dtype)");
+    MPX_CHECK_ARG(aligned16(ws), "workspace must be 16-byte aligned");
+    const int rc = radix_sort_pairs32(static_cast<uint32_t *>(keys), vals, n, dtype == MPX_SORT_F32 ? kRawF32 : kRawI32,
+                                      flags, ws, variant, s);
+    if (rc == MPX_ERR_UNSUPPORTED) set_error("sort_pairs variant %d needs ascending LDS lane order", variant);
+    return rc;
+}
+
 // Convenience form without a caller workspace (tools, one-off sorts): the
 // scratch is allocated for this call and freed after the stream drains.
 // Did a look-back wait of the last sort in `ws` give up (kSpinLimit)? Only
@@ -567,3 +689,12 @@ extern "C" int mpx_sort_ws(void *data, int64_t n, int dtype, void *workspace, in
 }
 
 extern "C" int mpx_sort_lane_order_ok(void *stream) { return mpx::lds_rtn_order_ok(mpx::as_stream(stream)); }
+
+extern "C" int64_t mpx_sort_pairs_workspace_bytes(int64_t n, int dtype) {
+    return mpx::sort_pairs_workspace_bytes(n, dtype);
+}
+
+extern "C" int mpx_sort_pairs_ws(void *keys, uint32_t *vals, int64_t n, int dtype, int flags, void *workspace,
+                                 int64_t workspace_bytes, void *stream) {
+    return mpx::sort_pairs_impl(keys, vals, n, dtype, flags, workspace, workspace_bytes, stream, 0);
+}

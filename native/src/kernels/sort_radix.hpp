@@ -18,6 +18,10 @@ namespace mpx {
 using SortRadixFn = int (*)(uint32_t *x, int64_t n, int mode, void *ws, int variant, hipStream_t s);
 int sort_impl(void *data, int64_t n, int dtype, void *ws, int64_t ws_bytes, void *stream, int variant,
               SortRadixFn radix);
+// the key-value sort behind mpx_sort_pairs_ws (sort.hip, sort_pairs.hpp);
+// variant 0 = AUTO, or 7 / 8 / 20 / 21 / 22 (mpx_sort_pairs_variant)
+int sort_pairs_impl(void *keys, uint32_t *vals, int64_t n, int dtype, int flags, void *ws, int64_t ws_bytes,
+                    void *stream, int variant);
 
 namespace {
 

@@ -800,6 +800,20 @@ extern "C" int mpx_sort_variant(void *data, int64_t n, int dtype, void *workspac
                           production ? nullptr : &mpx::tune_radix_sort32);
 }
 
+// The key-value sort with a fixed production ranking form and tile size:
+// 0 = AUTO, 7 / 8 the peer-mask fallback (8192 / 4096-key tiles), 20 / 21 / 22
+// the returning-add ranking with hot digits (8192 / 4096 / 16384-key tiles).
+// All of them run libmpx's pairs body; this entry only lets the tests and the
+// benchmarks pick one at any n.
+extern "C" int mpx_sort_pairs_variant(void *keys, uint32_t *vals, int64_t n, int dtype, int flags, void *workspace,
+                                      int64_t workspace_bytes, int variant, void *stream) {
+    if (variant != 0 && variant != 7 && variant != 8 && (variant < 20 || variant > 22)) {
+        mpx::set_error("sort_pairs variant %d: 0 (auto), 7, 8, 20, 21, 22", variant);
+        return MPX_ERR_ARG;
+    }
+    return mpx::sort_pairs_impl(keys, vals, n, dtype, flags, workspace, workspace_bytes, stream, variant);
+}
+
 extern "C" int mpx_sort_scatter_probe(const void *data, int64_t n, void *workspace, int64_t workspace_bytes, int knock,
                                       void *stream) {
     return mpx::scatter_probe(data, n, workspace, workspace_bytes, knock, stream);
