@@ -314,6 +314,12 @@ __global__ __launch_bounds__(64 * WPB) void jacobi_wave_kernel(const T *__restri
                 const V up = S[(UPW ? k + 2 : k) % 5], cen = S[(k + 1) % 5], dn = S[(UPW ? k : k + 2) % 5];
                 const T left = dpp_shift<T>(cen[NV - 1], 0x138);  // lane - 1's last element
                 const T right = dpp_shift<T>(cen[0], 0x130);      // lane + 1's first element
+                // rows outside the block (tail group) store nowhere: offset out of range
+                const bool rok = UPW ? r >= i0 : r < i1;
+                // without the tail exit the surplus steps of the last group run on
+                // clamped rows: their differences belong to no row of this block
+                bool counted = out_lane;
+                if constexpr (!TAIL_EXIT) counted = counted && rok;
                 V res;
 #pragma unroll
                 for (int e = 0; e < NV; ++e) {
@@ -324,10 +330,8 @@ __global__ __launch_bounds__(64 * WPB) void jacobi_wave_kernel(const T *__restri
                     const bool interior = j > 0 && j < cols - 1;
                     res[e] = interior ? sm : cen[e];
                     const T d = sm > cen[e] ? sm - cen[e] : cen[e] - sm;
-                    rmax = fmax(rmax, (interior && out_lane) ? d : (T)0);  // select + v_max: no exec branch
+                    rmax = fmax(rmax, (interior && counted) ? d : (T)0);  // select + v_max: no exec branch
                 }
-                // rows outside the block (tail group) store nowhere: offset out of range
-                const bool rok = UPW ? r >= i0 : r < i1;
                 const __amdgpu_buffer_rsrc_t orow = __builtin_amdgcn_make_buffer_rsrc(
                     un + (int64_t)(UPW ? max(r, i0) : min(r, i1 - 1)) * pitch, 0, cols * (int)sizeof(T), 0x00020000);
                 typedef uint32_t u4 __attribute__((ext_vector_type(4)));

@@ -426,7 +426,15 @@ def test_jacobi_sweep(gpu, dtype, shape):
         r_cpu = ops.jacobi_sweep(uc, unc, 1, rows + 1)
         assert float(res.item()) == r_cpu
     else:
+        # three correctly rounded adds in the kernel's association and an exact
+        # scale: the same expression in fp32 is the result bit for bit
+        u32 = u.to(dtype)
+        ref32 = ref.jacobi(u32, 1, rows + 1, keep_dtype=True)
+        assert ref32.dtype == dtype
+        assert torch.equal(got.view(torch.int32), ref32[1:rows + 1].view(torch.int32))
         assert torch.allclose(got.double(), un_ref[1:rows + 1], rtol=1e-6, atol=1e-6)
+        r_ref = (ref32[1:rows + 1, 1:-1] - u32[1:rows + 1, 1:-1]).abs().max()
+        assert float(res.item()) == float(r_ref)
 
 
 def test_fast_sqrt_exhaustive(gpu, capsys):
