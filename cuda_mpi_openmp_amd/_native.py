@@ -89,6 +89,11 @@ _SIGNATURES = {
     "mpx_jacobi_sync_bytes": (c_int, []),
     "mpx_jacobi_peer_sweep": (c_int, [c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "mpx_jacobi_f32": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    # Poisson sweeps: (u, b, un, ...) with the right-hand side b laid out like u
+    "mpx_jacobi_rhs_f64": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "mpx_jacobi_rhs_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "mpx_jacobi_peer_sweep_rhs": (c_int, [c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "mpx_cpu_jacobi_rhs_f64": (ctypes.c_double, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int]),
     "mpx_cpu_threads": (c_int, []),
     "mpx_cpu_vsub_f64": (None, [c_vp, c_vp, c_vp, c_i64]),
     "mpx_cpu_vsub_f32": (None, [c_vp, c_vp, c_vp, c_i64]),
@@ -135,6 +140,9 @@ _TUNE_SIGNATURES = {
     # lab1 / Jacobi tuning variants (native/tune/{vsub,jacobi}_variants.hip)
     "mpx_vsub_variant": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp]),
     "mpx_jacobi_variant": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp]),
+    # (u, b, un, cols, pitch, r0, r1, resid, fp64, R, nt, stream)
+    "mpx_jacobi_rhs_variant": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
+                                       c_vp]),
 }
 _tune = None
 

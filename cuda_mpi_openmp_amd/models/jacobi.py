@@ -1,5 +1,7 @@
-"""2-D Jacobi solver for the Laplace equation on a row-slab decomposed grid —
-the distributed-stencil north star of BASELINE.json ("MPI -> RCCL 2D Jacobi
+"""2-D Jacobi solver on a row-slab decomposed grid: the Laplace equation by
+default, the Poisson equation -Laplace(u) = f once a right-hand side is set
+(``SlabJacobi.set_rhs``, b = h^2 f; every transport, graphs and checkpoints
+carry it) — the distributed-stencil north star of BASELINE.json ("MPI -> RCCL 2D Jacobi
 stencil, 16384^2 grid domain-decomposed across 8 MI355X, halo exchange over
 xGMI"). The reference has no such solver; this is its MI355X-native
 form.
@@ -47,6 +49,14 @@ from ..parallel.slab import Slab
 
 
 class SlabJacobi:
+    """Jacobi iteration on this rank's row slab. Laplace by default:
+    u <- ((up + down) + (left + right)) / 4. With a right-hand side
+    (``set_rhs``: b = h^2 f for -Laplace(u) = f) it solves the Poisson problem:
+    u <- (((up + down) + (left + right)) + b) / 4, whose fixed point satisfies
+    4 u - (sum of the neighbours) = b. The right-hand side is local to each
+    rank (never exchanged); a solver that never sets one launches exactly the
+    Laplace sweeps."""
+
     def __init__(self, ctx: DistContext, global_rows: int, cols: int, dtype=torch.float64, check_every: int = 10,
                  overlap: bool | str = "auto", halo: str = "auto"):
         if cols < 3:
@@ -94,6 +104,7 @@ class SlabJacobi:
             self.u = torch.zeros(shape, dtype=dtype, device=dev)
             self.un = torch.zeros(shape, dtype=dtype, device=dev)
         self.resid = torch.zeros(1, dtype=dtype, device=dev)
+        self.rhs: Optional[torch.Tensor] = None  # (buffer_rows, cols) once set_rhs has run
         self.iteration = 0
         self.last_residual: Optional[float] = None
         self._halos_valid = False  # u's halo rows hold the neighbours' current rows
@@ -123,6 +134,31 @@ class SlabJacobi:
         self.u[1:1 + s.rows, 1:-1] = vals.to(self.dtype)
         self.un.copy_(self.u)
         self._halos_valid = False
+
+    def set_rhs(self, fn: Optional[Callable[[torch.Tensor, torch.Tensor], torch.Tensor]] = None,
+                tensor: Optional[torch.Tensor] = None) -> None:
+        """Right-hand side b = h^2 f of -Laplace(u) = f on this rank's rows:
+        ``fn(global_row_index, col_index)`` with ``fill``'s conventions (interior
+        columns), or ``tensor``, this rank's owned rows as (rows, cols). The
+        buffer has u's shape; its halo rows and boundary columns are never
+        read for a result. The cached cycle graphs hold the Laplace launches
+        (or none), so they are dropped."""
+        if (fn is None) == (tensor is None):
+            raise ValueError("set_rhs takes exactly one of fn and tensor")
+        s = self.slab
+        if tensor is not None and tuple(tensor.shape) != (s.rows, self.cols):
+            raise ValueError(f"rhs tensor must hold this rank's owned rows, shape {(s.rows, self.cols)}")
+        self._quiesce()
+        self._graphs.clear()
+        if self.rhs is None:
+            self.rhs = torch.zeros((s.buffer_rows, self.cols), dtype=self.dtype, device=self.u.device)
+        if tensor is not None:
+            self.rhs[1:1 + s.rows] = tensor.to(self.u.device, self.dtype)
+        else:
+            rows = torch.arange(s.row0, s.row0 + s.rows, device=self.u.device).unsqueeze(1)
+            cols = torch.arange(1, self.cols - 1, device=self.u.device).unsqueeze(0)
+            vals = torch.as_tensor(fn(rows, cols), device=self.u.device)
+            self.rhs[1:1 + s.rows, 1:-1] = vals.to(self.dtype)
 
     @property
     def transport(self) -> Optional[str]:
@@ -175,9 +211,9 @@ class SlabJacobi:
         if r1 <= r0:
             return
         if self.u.is_cuda:
-            ops.jacobi_sweep(self.u, self.un, r0, r1, self.resid if track else None)
+            ops.jacobi_sweep(self.u, self.un, r0, r1, self.resid if track else None, rhs=self.rhs)
         else:
-            r = ops.jacobi_sweep(self.u, self.un, r0, r1)
+            r = ops.jacobi_sweep(self.u, self.un, r0, r1, rhs=self.rhs)
             if track:
                 self.resid.fill_(max(float(self.resid.item()), r))
 
@@ -215,9 +251,16 @@ class SlabJacobi:
         if self.peer is not None:
             from .. import _native
 
-            _native.check(_native.lib().mpx_jacobi_peer_sweep(
-                int(self.dtype == torch.float64), self.u.data_ptr(), self.un.data_ptr(), self.cols, self.cols, n,
-                self.resid.data_ptr() if track else None, ctypes.byref(self.peer.desc), _native.stream_of(self.u)))
+            if self.rhs is not None:  # b is local: same descriptor, same counters
+                _native.check(_native.lib().mpx_jacobi_peer_sweep_rhs(
+                    int(self.dtype == torch.float64), self.u.data_ptr(), self.rhs.data_ptr(), self.un.data_ptr(),
+                    self.cols, self.cols, n, self.resid.data_ptr() if track else None,
+                    ctypes.byref(self.peer.desc), _native.stream_of(self.u)))
+            else:
+                _native.check(_native.lib().mpx_jacobi_peer_sweep(
+                    int(self.dtype == torch.float64), self.u.data_ptr(), self.un.data_ptr(), self.cols, self.cols, n,
+                    self.resid.data_ptr() if track else None, ctypes.byref(self.peer.desc),
+                    _native.stream_of(self.u)))
         elif self.ctx.is_distributed and self.overlap:
             edge = [1] if n == 1 else [1, n]
             for r in edge:
@@ -307,10 +350,14 @@ class SlabJacobi:
         return gather_slabs(self.owned.contiguous(), self.slab, self.ctx)
 
     def save_checkpoint(self, prefix: str) -> str:
-        """One file per rank: owned rows (+ halos), iteration, residual."""
+        """One file per rank: owned rows (+ halos), iteration, residual and,
+        when one is set, the right-hand side."""
         path = f"{prefix}.rank{self.ctx.rank}.pt"
-        torch.save({"u": self.u.cpu(), "iteration": self.iteration, "residual": self.last_residual,
-                    "global_rows": self.slab.global_rows, "world": self.ctx.world, "cols": self.cols}, path)
+        ck = {"u": self.u.cpu(), "iteration": self.iteration, "residual": self.last_residual,
+              "global_rows": self.slab.global_rows, "world": self.ctx.world, "cols": self.cols}
+        if self.rhs is not None:
+            ck["rhs"] = self.rhs.cpu()
+        torch.save(ck, path)
         return path
 
     def close(self) -> None:
@@ -328,6 +375,10 @@ class SlabJacobi:
         self._graphs.clear()
         self.u.copy_(ck["u"].to(self.u.device, self.dtype))
         self.un.copy_(self.u)
+        if "rhs" in ck:  # checkpoints without one leave this solver's rhs alone
+            if self.rhs is None:
+                self.rhs = torch.zeros_like(self.u)
+            self.rhs.copy_(ck["rhs"].to(self.u.device, self.dtype))
         self.iteration = int(ck["iteration"])
         self.last_residual = ck["residual"]
         self._halos_valid = False

@@ -104,15 +104,24 @@ def classify(img: torch.Tensor, mu: np.ndarray, inv: np.ndarray, device=None) ->
     return out.reshape(img.shape)
 
 
-def jacobi(u: torch.Tensor, r0: int, r1: int, keep_dtype: bool = False) -> torch.Tensor:
+def jacobi(u: torch.Tensor, r0: int, r1: int, keep_dtype: bool = False,
+           rhs: torch.Tensor | None = None) -> torch.Tensor:
     """One sweep over rows [r0, r1) (1-based, halo rows at 0 and rows+1), in
     fp64, or with ``keep_dtype`` in u's own dtype: three correctly rounded adds
     in the kernels' association and an exact scale, so the native result must
-    equal it bit for bit."""
+    equal it bit for bit. ``rhs`` (u's shape; b = h^2 f of -Laplace(u) = f) is
+    a fourth correctly rounded add after the neighbours:
+    (((up + down) + (left + right)) + b) * 0.25."""
     u = u.cpu() if keep_dtype else u.cpu().to(torch.float64)
     un = u.clone()
     c = u[r0:r1, 1:-1]
-    s = ((u[r0 - 1:r1 - 1, 1:-1] + u[r0 + 1:r1 + 1, 1:-1]) + (u[r0:r1, :-2] + u[r0:r1, 2:])) * 0.25
+    s = (u[r0 - 1:r1 - 1, 1:-1] + u[r0 + 1:r1 + 1, 1:-1]) + (u[r0:r1, :-2] + u[r0:r1, 2:])
+    if rhs is not None:
+        b = rhs.cpu().to(u.dtype)
+        if b.shape != u.shape:
+            raise ValueError("rhs must have u's shape")
+        s = s + b[r0:r1, 1:-1]
+    s = s * 0.25
     un[r0:r1, 1:-1] = s
     del c
     return un

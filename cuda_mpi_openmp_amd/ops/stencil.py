@@ -16,13 +16,22 @@ from .. import _native
 
 
 def jacobi_sweep(u: torch.Tensor, un: torch.Tensor, r0: int, r1: int,
-                 resid: Optional[torch.Tensor] = None) -> Optional[float]:
+                 resid: Optional[torch.Tensor] = None, rhs: Optional[torch.Tensor] = None) -> Optional[float]:
     """GPU: enqueue the sweep (resid, a 1-element tensor zeroed by the caller,
-    accumulates the max on device). CPU: run it and return the residual."""
+    accumulates the max on device). CPU: run it and return the residual.
+
+    ``rhs`` (u's shape, dtype and device, contiguous): the Poisson sweep
+    un = (((up + down) + (left + right)) + rhs) * 0.25 for -Laplace(u) = f with
+    rhs = h^2 f; read at the interior points of rows [r0, r1) only."""
     if u.shape != un.shape or u.dim() != 2 or u.dtype != un.dtype:
         raise ValueError("u/un must be matching 2-D tensors")
     if not (u.is_contiguous() and un.is_contiguous()):
         raise ValueError("u/un must be contiguous")
+    if rhs is not None:
+        if not isinstance(rhs, torch.Tensor) or rhs.shape != u.shape or rhs.dtype != u.dtype or rhs.device != u.device:
+            raise ValueError("rhs must match u's shape, dtype and device")
+        if not rhs.is_contiguous():
+            raise ValueError("rhs must be contiguous")
     rows2, cols = u.shape
     if not (1 <= r0 <= r1 <= rows2 - 1):
         raise ValueError("rows out of range")
@@ -31,7 +40,12 @@ def jacobi_sweep(u: torch.Tensor, un: torch.Tensor, r0: int, r1: int,
         rp = 0 if resid is None else resid.data_ptr()
         if resid is not None and (resid.dtype != u.dtype or resid.device != u.device):
             raise ValueError("resid must match u's dtype and device")
-        if u.dtype == torch.float64:
+        if u.dtype not in (torch.float64, torch.float32):
+            raise ValueError("jacobi supports float64/float32")
+        if rhs is not None:
+            fn = L.mpx_jacobi_rhs_f64 if u.dtype == torch.float64 else L.mpx_jacobi_rhs_f32
+            _native.check(fn(u.data_ptr(), rhs.data_ptr(), un.data_ptr(), cols, cols, r0, r1, rp, _native.stream_of(u)))
+        elif u.dtype == torch.float64:
             _native.check(L.mpx_jacobi_f64(u.data_ptr(), un.data_ptr(), cols, cols, r0, r1, rp, _native.stream_of(u)))
         elif u.dtype == torch.float32:
             _native.check(L.mpx_jacobi_f32(u.data_ptr(), un.data_ptr(), cols, cols, r0, r1, rp, _native.stream_of(u)))
@@ -40,7 +54,10 @@ def jacobi_sweep(u: torch.Tensor, un: torch.Tensor, r0: int, r1: int,
         return None
     if u.dtype != torch.float64:
         raise ValueError("CPU jacobi reference is float64")
-    r = L.mpx_cpu_jacobi_f64(u.data_ptr(), un.data_ptr(), cols, cols, r0, r1)
+    if rhs is not None:
+        r = L.mpx_cpu_jacobi_rhs_f64(u.data_ptr(), rhs.data_ptr(), un.data_ptr(), cols, cols, r0, r1)
+    else:
+        r = L.mpx_cpu_jacobi_f64(u.data_ptr(), un.data_ptr(), cols, cols, r0, r1)
     if resid is not None:
         resid.fill_(max(float(resid.item()), r))
     return r

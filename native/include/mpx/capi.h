@@ -304,6 +304,22 @@ int mpx_jacobi_f64(const double *u, double *un, int cols, int pitch, int r0, int
                    double *resid, void *stream);
 int mpx_jacobi_f32(const float *u, float *un, int cols, int pitch, int r0, int r1, float *resid,
                    void *stream);
+/* Poisson sweeps (-Laplace(u) = f): the same sweeps with a right-hand side `b`
+ * laid out like u (same shape and pitch), b = h^2 * f already scaled by the
+ * mesh width:
+ *   un[i][j] = (((u[i-1][j] + u[i+1][j]) + (u[i][j-1] + u[i][j+1])) + b[i][j]) * 0.25
+ * in exactly this association (four correctly rounded adds, an exact scale),
+ * so fp32, fp64 and the CPU reference agree bit for bit with a plain
+ * expression. b is read at the interior points of the swept rows only: its
+ * halo rows and boundary columns are don't-care. A NULL b is an argument
+ * error; a b that is not 16-byte aligned takes the scalar kernel (the peer
+ * sweep refuses it). The residual stays max|un - u|. */
+int mpx_jacobi_rhs_f64(const double *u, const double *b, double *un, int cols, int pitch, int r0, int r1,
+                       double *resid, void *stream);
+int mpx_jacobi_rhs_f32(const float *u, const float *b, float *un, int cols, int pitch, int r0, int r1,
+                       float *resid, void *stream);
+int mpx_jacobi_peer_sweep_rhs(int fp64, void *u, const void *b, void *un, int cols, int pitch, int rows,
+                              void *resid, const mpx_jacobi_peer *p, void *stream);
 
 /* ---------------- lab5: ascending sort (no reference program) ---------------- */
 /* In place on the device; dtype is an mpx_sort_dtype. int32/float32: LSD radix sort
@@ -354,6 +370,8 @@ void mpx_cpu_conv(const uint32_t *in, uint32_t *out, int w, int pitch, int oy0, 
                   int y_hi, int k, int anchor, int mode, const float *wx, const float *wy);
 void mpx_cpu_classify(uint32_t *img, int64_t npix, int nc, const double *mu, const double *inv);
 double mpx_cpu_jacobi_f64(const double *u, double *un, int cols, int pitch, int r0, int r1);
+/* with the right-hand side of mpx_jacobi_rhs_f64; NaN when b is NULL */
+double mpx_cpu_jacobi_rhs_f64(const double *u, const double *b, double *un, int cols, int pitch, int r0, int r1);
 void mpx_cpu_sort(void *data, int64_t n, int dtype);
 void mpx_cpu_sort_pairs(void *keys, uint32_t *vals, int64_t n, int dtype, int flags);
 

@@ -24,13 +24,17 @@
 namespace mpx {
 namespace {
 
-template <typename T>
-int launch_jacobi(const T *u, T *un, int cols, int pitch, int r0, int r1, T *resid, void *stream) {
-    MPX_CHECK_ARG(u && un, "null pointer");
+// RHS: the Poisson sweep (((up + dn) + (l + r)) + b) * 0.25 with the source
+// term b laid out like u; same path selection, b's alignment included
+template <typename T, bool RHS = false>
+int launch_jacobi(const T *u, T *un, int cols, int pitch, int r0, int r1, T *resid, void *stream,
+                  const T *b = nullptr) {
+    MPX_CHECK_ARG(u && un && (!RHS || b), "null pointer");
     MPX_CHECK_ARG(cols >= 1 && pitch >= cols && r0 >= 1 && r1 >= r0, "bad slab geometry");
     if (r1 == r0) return MPX_OK;
     constexpr int NV = JVec<T>::n;
-    if ((pitch % NV == 0) && (cols % NV == 0) && aligned16(u) && aligned16(un)) {
+    const bool al16 = aligned16(u) && aligned16(un) && (!RHS || aligned16(b));
+    if ((pitch % NV == 0) && (cols % NV == 0) && al16) {
         const int strips = (cols / NV + kStripVec - 1) / kStripVec;
         const int rows = r1 - r0;
         // 8 rows per wave, odd row blocks walking up (ALT: two vertically
@@ -42,34 +46,37 @@ int launch_jacobi(const T *u, T *un, int cols, int pitch, int r0, int r1, T *res
         int R = kJacobiRows;
         while (R > 1 && (int64_t)strips * ((rows + R - 1) / R) < 16384) R >>= 1;
         const int nwaves = strips * ((rows + R - 1) / R);
-        hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 0, true, false, true>), dim3((nwaves + 3) / 4), dim3(256), 0,
-                           as_stream(stream), u, un, cols, pitch, r0, r1, strips, R, nwaves, resid, mpx_jacobi_peer{});
+        hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 0, true, false, true, 4, RHS, RHS && kRhsNT>),
+                           dim3((nwaves + 3) / 4), dim3(256), 0, as_stream(stream), u, un, cols, pitch, r0, r1, strips, R, nwaves, resid,
+                           mpx_jacobi_peer{}, b);
         MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
         return MPX_OK;
     }
-    const bool vec = (pitch % NV == 0) && aligned16(u) && aligned16(un);
+    const bool vec = (pitch % NV == 0) && al16;
     const int lanes = vec ? (cols + NV - 1) / NV : cols;
     const dim3 blk(256);
     const dim3 grd((lanes + 255) / 256, (r1 - r0 + kRows - 1) / kRows);
     if (vec)
-        hipLaunchKernelGGL((jacobi_kernel<T, true>), grd, blk, 0, as_stream(stream), u, un, cols, pitch, r0, r1, resid);
+        hipLaunchKernelGGL((jacobi_kernel<T, true, RHS>), grd, blk, 0, as_stream(stream), u, un, cols, pitch, r0, r1,
+                           resid, b);
     else
-        hipLaunchKernelGGL((jacobi_kernel<T, false>), grd, blk, 0, as_stream(stream), u, un, cols, pitch, r0, r1,
-                           resid);
+        hipLaunchKernelGGL((jacobi_kernel<T, false, RHS>), grd, blk, 0, as_stream(stream), u, un, cols, pitch, r0, r1,
+                           resid, b);
     MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
     return MPX_OK;
 }
 
-template <typename T>
+template <typename T, bool RHS = false>
 int launch_jacobi_peer(const T *u, T *un, int cols, int pitch, int rows, T *resid, const mpx_jacobi_peer &pr,
-                       void *stream) {
-    MPX_CHECK_ARG(u && un && pr.sync, "null pointer");
+                       void *stream, const T *b = nullptr) {
+    MPX_CHECK_ARG(u && un && pr.sync && (!RHS || b), "null pointer");
     MPX_CHECK_ARG(cols >= 1 && pitch >= cols && rows >= 1, "bad slab geometry");
     MPX_CHECK_ARG(!pr.up_flag == !pr.up_row[0] && !pr.up_row[0] == !pr.up_row[1], "up neighbour: rows and flag together");
     MPX_CHECK_ARG(!pr.dn_flag == !pr.dn_row[0] && !pr.dn_row[0] == !pr.dn_row[1], "down neighbour: rows and flag together");
     constexpr int NV = JVec<T>::n;
     MPX_CHECK_ARG(pitch % NV == 0 && cols % NV == 0 && aligned16(u) && aligned16(un),
                   "peer halos need the 16-byte vector layout (cols and pitch multiples of the vector width)");
+    MPX_CHECK_ARG(!RHS || aligned16(b), "peer halos need the 16-byte vector layout (right-hand side not aligned)");
     for (const void *q : {pr.up_row[0], pr.up_row[1], pr.dn_row[0], pr.dn_row[1], (const void *)pr.mb_first[0],
                           (const void *)pr.mb_first[1], (const void *)pr.mb_last[0], (const void *)pr.mb_last[1]})
         MPX_CHECK_ARG(!q || aligned16(q), "neighbour and mailbox rows must be 16-byte aligned");
@@ -81,8 +88,8 @@ int launch_jacobi_peer(const T *u, T *un, int cols, int pitch, int rows, T *resi
     int R = kJacobiRows;
     while (R > 1 && (int64_t)strips * ((rows + R - 1) / R) < 16384) R >>= 1;
     const int nwaves = strips * ((rows + R - 1) / R);
-    hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 0, true, true, true>), dim3((nwaves + 3) / 4), dim3(256), 0,
-                       as_stream(stream), u, un, cols, pitch, 1, rows + 1, strips, R, nwaves, resid, pr);
+    hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 0, true, true, true, 4, RHS, RHS && kRhsNT>), dim3((nwaves + 3) / 4),
+                       dim3(256), 0, as_stream(stream), u, un, cols, pitch, 1, rows + 1, strips, R, nwaves, resid, pr, b);
     MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
     return MPX_OK;
 }
@@ -110,6 +117,27 @@ extern "C" int mpx_jacobi_peer_sweep(int fp64, void *u, void *un, int cols, int 
         return launch_jacobi_peer<double>((const double *)u, (double *)un, cols, pitch, rows, (double *)resid, *p,
                                           stream);
     return launch_jacobi_peer<float>((const float *)u, (float *)un, cols, pitch, rows, (float *)resid, *p, stream);
+}
+
+extern "C" int mpx_jacobi_rhs_f64(const double *u, const double *b, double *un, int cols, int pitch, int r0, int r1,
+                                  double *resid, void *stream) {
+    return mpx::launch_jacobi<double, true>(u, un, cols, pitch, r0, r1, resid, stream, b);
+}
+
+extern "C" int mpx_jacobi_rhs_f32(const float *u, const float *b, float *un, int cols, int pitch, int r0, int r1,
+                                  float *resid, void *stream) {
+    return mpx::launch_jacobi<float, true>(u, un, cols, pitch, r0, r1, resid, stream, b);
+}
+
+extern "C" int mpx_jacobi_peer_sweep_rhs(int fp64, void *u, const void *b, void *un, int cols, int pitch, int rows,
+                                         void *resid, const mpx_jacobi_peer *p, void *stream) {
+    using namespace mpx;
+    MPX_CHECK_ARG(p, "null peer descriptor");
+    if (fp64)
+        return launch_jacobi_peer<double, true>((const double *)u, (double *)un, cols, pitch, rows, (double *)resid, *p,
+                                                stream, (const double *)b);
+    return launch_jacobi_peer<float, true>((const float *)u, (float *)un, cols, pitch, rows, (float *)resid, *p, stream,
+                                           (const float *)b);
 }
 
 extern "C" int mpx_jacobi_sync_bytes(void) { return 4 * 128; }

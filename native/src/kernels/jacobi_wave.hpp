@@ -41,9 +41,13 @@ __device__ __forceinline__ T lane_of(const typename JVec<T>::type &v, int i) {
     else return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w));
 }
 
-template <typename T, bool VEC>
+// RHS: Poisson source term b (laid out like u, already scaled by h^2), added
+// after the four neighbours: (((up + dn) + (l + r)) + b) * 0.25. b is read at
+// interior points of the swept rows only; RHS = false never touches it.
+template <typename T, bool VEC, bool RHS = false>
 __global__ __launch_bounds__(256) void jacobi_kernel(const T *__restrict__ u, T *__restrict__ un, int cols,
-                                                     int pitch, int r0, int r1, T *__restrict__ resid) {
+                                                     int pitch, int r0, int r1, T *__restrict__ resid,
+                                                     const T *__restrict__ b) {
     using V = typename JVec<T>::type;
     constexpr int NV = VEC ? JVec<T>::n : 1;
     const int j0 = NV * (blockIdx.x * blockDim.x + threadIdx.x);
@@ -73,12 +77,31 @@ __global__ __launch_bounds__(256) void jacobi_kernel(const T *__restrict__ u, T 
             const T left = j0 > 0 ? crow[j0 - 1] : (T)0;
             const T right = (j0 + NV < cols) ? crow[j0 + NV] : (T)0;
             T res[NV];
+            T src[NV];
+            if constexpr (RHS) {
+                const T *brow = b + (int64_t)i * pitch;
+                bool loaded = false;
+                if constexpr (VEC) {
+                    if (j0 + NV <= cols) {
+                        const V q = *reinterpret_cast<const V *>(brow + j0);
+#pragma unroll
+                        for (int k = 0; k < NV; ++k) src[k] = lane_of<T>(q, k);
+                        loaded = true;
+                    }
+                }
+                if (!loaded) {
+#pragma unroll
+                    for (int k = 0; k < NV; ++k) src[k] = (j0 + k < cols) ? brow[j0 + k] : (T)0;
+                }
+            }
 #pragma unroll
             for (int k = 0; k < NV; ++k) {
                 const int j = j0 + k;
                 const T l = k == 0 ? left : cen[k - 1];
                 const T r = k == NV - 1 ? right : cen[k + 1];
-                const T s = ((up[k] + dn[k]) + (l + r)) * (T)0.25;
+                T s;
+                if constexpr (RHS) s = (((up[k] + dn[k]) + (l + r)) + src[k]) * (T)0.25;
+                else s = ((up[k] + dn[k]) + (l + r)) * (T)0.25;
                 const bool interior = j > 0 && j < cols - 1;
                 res[k] = interior ? s : cen[k];
                 if (interior && j < cols) {
@@ -126,6 +149,10 @@ __global__ __launch_bounds__(256) void jacobi_kernel(const T *__restrict__ u, T 
 constexpr int kStripVec = 62;             // output vectors per wave
 constexpr int kJacobiRows = 8;            // rows per wave (row block) of the production sweeps
 constexpr uint32_t kDrop = 0x7ffffff0u;   // buffer offset past any range: store dropped
+// production loads of the source term b: non-temporal. b is read once per sweep
+// and shared with no other row block; 16384^2, same process, interleaved rounds
+// (profiles/jacobi.md): fp64 1142 us vs 1187 plain, fp32 548 vs 557
+constexpr bool kRhsNT = true;
 
 template <typename T> struct JWide;
 template <> struct JWide<double> { typedef double type __attribute__((ext_vector_type(2))); };
@@ -216,11 +243,19 @@ __device__ __forceinline__ T wave_max_dpp(T v) {
 // LNT: 0 plain loads, 1 every row non-temporal (tuning), 2 only the rows no
 // neighbouring row block reads (i0 + 1 .. i1 - 2), the conv band kernel's
 // round-3 default for separable windows
+// RHS: source term b (u's shape and pitch) in a second 5-slot ring indexed like
+// the u ring: the step that prefetches u's row r +- 3 into slot (k + 4) % 5
+// prefetches b's row too, and reads its own b from cen's slot (k + 1) % 5. Only
+// rows of the block ever serve as cen, so b's rows are clamped to [i0, i1 - 1]
+// (u's to [i0 - 1, i1]) and slot 0 has no prologue load: b is read once per
+// sweep, halo rows and all of b outside [r0, r1) never. BNT: those loads
+// non-temporal (tuning A/B). b is purely local, also with PEER.
 template <typename T, int AUX = 0, int LNT = 0, bool TAIL_EXIT = true, bool PEER = false, bool ALT = false,
-          int WPB = 4>
+          int WPB = 4, bool RHS = false, bool BNT = false>
 __global__ __launch_bounds__(64 * WPB) void jacobi_wave_kernel(const T *__restrict__ u, T *__restrict__ un, int cols,
                                                           int pitch, int r0, int r1, int strips, int rows_per_wave,
-                                                          int nwaves, T *__restrict__ resid, mpx_jacobi_peer pr) {
+                                                          int nwaves, T *__restrict__ resid, mpx_jacobi_peer pr,
+                                                          const T *__restrict__ b) {
     using V = typename JWide<T>::type;
     constexpr int NV = JVec<T>::n;
     const int lane = threadIdx.x & 63;
@@ -280,6 +315,11 @@ __global__ __launch_bounds__(64 * WPB) void jacobi_wave_kernel(const T *__restri
             }
             return *p;
         };
+        auto ldb = [&](int i) {
+            const V *p = reinterpret_cast<const V *>(b + (int64_t)cvc * NV + (int64_t)i * pitch);
+            if constexpr (BNT) return __builtin_nontemporal_load(p);
+            return *p;
+        };
         const uint32_t soff = out_lane ? (uint32_t)(cv * NV * sizeof(T)) : kDrop;
         const int j0 = cv * NV;
         // One walk over the block's rows, prologue included (each direction its
@@ -305,12 +345,27 @@ __global__ __launch_bounds__(64 * WPB) void jacobi_wave_kernel(const T *__restri
                 S[3] = ld(min(i0 + 2, i1));
             }
             S[4] = V{};  // first written by step 0; a copy of S[3] would wait on its load
+            V B[RHS ? 5 : 1];
+            if constexpr (RHS) {
+                B[0] = V{};  // the slot of x_{i0-1} (x_{i1}): never a centre row
+                if constexpr (UPW) {
+                    B[1] = ldb(i1 - 1);
+                    B[2] = ldb(max(i1 - 2, i0));
+                    B[3] = ldb(max(i1 - 3, i0));
+                } else {
+                    B[1] = ldb(i0);
+                    B[2] = ldb(min(i0 + 1, i1 - 1));
+                    B[3] = ldb(min(i0 + 2, i1 - 1));
+                }
+                B[4] = V{};
+            }
             __builtin_amdgcn_sched_barrier(0);
             auto step = [&](auto kc, int i) {
                 constexpr int k = decltype(kc)::value;
                 const int r = UPW ? i - k : i + k;  // row computed in this step
                 // x_{r+3} replaces x_{r-2} (walking up: x_{r-3} replaces x_{r+2})
                 S[(k + 4) % 5] = UPW ? ld(max(r - 3, i0 - 1)) : ld(min(r + 3, i1));
+                if constexpr (RHS) B[(k + 4) % 5] = UPW ? ldb(max(r - 3, i0)) : ldb(min(r + 3, i1 - 1));
                 const V up = S[(UPW ? k + 2 : k) % 5], cen = S[(k + 1) % 5], dn = S[(UPW ? k : k + 2) % 5];
                 const T left = dpp_shift<T>(cen[NV - 1], 0x138);  // lane - 1's last element
                 const T right = dpp_shift<T>(cen[0], 0x130);      // lane + 1's first element
@@ -326,7 +381,9 @@ __global__ __launch_bounds__(64 * WPB) void jacobi_wave_kernel(const T *__restri
                     const int j = j0 + e;
                     const T l = e == 0 ? left : cen[e - 1];
                     const T rr = e == NV - 1 ? right : cen[e + 1];
-                    const T sm = ((up[e] + dn[e]) + (l + rr)) * (T)0.25;
+                    T sm;
+                    if constexpr (RHS) sm = (((up[e] + dn[e]) + (l + rr)) + B[(k + 1) % 5][e]) * (T)0.25;
+                    else sm = ((up[e] + dn[e]) + (l + rr)) * (T)0.25;
                     const bool interior = j > 0 && j < cols - 1;
                     res[e] = interior ? sm : cen[e];
                     const T d = sm > cen[e] ? sm - cen[e] : cen[e] - sm;

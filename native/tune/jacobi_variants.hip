@@ -23,22 +23,23 @@ extern "C" int mpx_jacobi_variant(void *u, void *un, int cols, int pitch, int r0
     hipStream_t s = as_stream(stream);
 #define MPX_JV(T, A)                                                                                          \
     hipLaunchKernelGGL((jacobi_wave_kernel<T, A>), g, b, 0, s, (const T *)u, (T *)un, cols, pitch, r0, r1, strips, \
-                       R, nwaves, (T *)resid, mpx_jacobi_peer{})
+                       R, nwaves, (T *)resid, mpx_jacobi_peer{}, (const T *)nullptr)
 #define MPX_JVN(T)                                                                                             \
     hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 1>), g, b, 0, s, (const T *)u, (T *)un, cols, pitch, r0, r1,    \
-                       strips, R, nwaves, (T *)resid, mpx_jacobi_peer{})
+                       strips, R, nwaves, (T *)resid, mpx_jacobi_peer{}, (const T *)nullptr)
 #define MPX_JVA(T)                                                                                             \
     hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 0, true, false, true>), g, b, 0, s, (const T *)u, (T *)un, cols,  \
-                       pitch, r0, r1, strips, R, nwaves, (T *)resid, mpx_jacobi_peer{})
+                       pitch, r0, r1, strips, R, nwaves, (T *)resid, mpx_jacobi_peer{}, (const T *)nullptr)
 #define MPX_JVW(T)                                                                                             \
     hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 0, true, false, true, 16>), dim3((nwaves + 15) / 16), dim3(1024),  \
-                       0, s, (const T *)u, (T *)un, cols, pitch, r0, r1, strips, R, nwaves, (T *)resid, mpx_jacobi_peer{})
+                       0, s, (const T *)u, (T *)un, cols, pitch, r0, r1, strips, R, nwaves, (T *)resid,               \
+                       mpx_jacobi_peer{}, (const T *)nullptr)
 #define MPX_JVI(T)                                                                                             \
     hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 2, true, false, true>), g, b, 0, s, (const T *)u, (T *)un, cols,  \
-                       pitch, r0, r1, strips, R, nwaves, (T *)resid, mpx_jacobi_peer{})
+                       pitch, r0, r1, strips, R, nwaves, (T *)resid, mpx_jacobi_peer{}, (const T *)nullptr)
 #define MPX_JVX(T)                                                                                             \
     hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 0, false>), g, b, 0, s, (const T *)u, (T *)un, cols, pitch, r0, \
-                       r1, strips, R, nwaves, (T *)resid, mpx_jacobi_peer{})
+                       r1, strips, R, nwaves, (T *)resid, mpx_jacobi_peer{}, (const T *)nullptr)
     if (fp64) {
         if (aux == 22) MPX_JVI(double); else if (aux == 50) MPX_JVW(double); else if (aux == 18) MPX_JVA(double); else if (aux == 10) MPX_JVX(double); else if (aux == 6) MPX_JVN(double); else if (aux) MPX_JV(double, 2); else MPX_JV(double, 0);
     } else {
@@ -50,6 +51,35 @@ extern "C" int mpx_jacobi_variant(void *u, void *un, int cols, int pitch, int r0
 #undef MPX_JVI
 #undef MPX_JVA
 #undef MPX_JVW
+    MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
+    return MPX_OK;
+}
+
+// The production template with a source term, <T, 2, 0, true, false, true, 4,
+// RHS = true>, at an explicit rows-per-wave R (row-block tests) and with plain
+// (nt = 0) or non-temporal (nt = 1) loads of b (the A/B of profiles/jacobi.md).
+extern "C" int mpx_jacobi_rhs_variant(void *u, const void *b, void *un, int cols, int pitch, int r0, int r1,
+                                      void *resid, int fp64, int R, int nt, void *stream) {
+    using namespace mpx;
+    MPX_CHECK_ARG(u && b && un && cols >= 1 && pitch >= cols && r0 >= 1 && r1 >= r0 && R >= 1, "bad arguments");
+    MPX_CHECK_ARG(nt == 0 || nt == 1, "nt must be 0 (plain loads of b) or 1 (non-temporal)");
+    const int NV = fp64 ? 2 : 4;
+    MPX_CHECK_ARG(pitch % NV == 0 && cols % NV == 0 && aligned16(u) && aligned16(b) && aligned16(un),
+                  "needs the vector layout");
+    if (r1 == r0) return MPX_OK;
+    const int strips = (cols / NV + kStripVec - 1) / kStripVec;
+    const int nwaves = strips * ((r1 - r0 + R - 1) / R);
+    const dim3 g((nwaves + 3) / 4), blk(256);
+    hipStream_t s = as_stream(stream);
+#define MPX_JR(T, NT)                                                                                            \
+    hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 0, true, false, true, 4, true, NT>), g, blk, 0, s, (const T *)u, \
+                       (T *)un, cols, pitch, r0, r1, strips, R, nwaves, (T *)resid, mpx_jacobi_peer{}, (const T *)b)
+    if (fp64) {
+        if (nt) MPX_JR(double, true); else MPX_JR(double, false);
+    } else {
+        if (nt) MPX_JR(float, true); else MPX_JR(float, false);
+    }
+#undef MPX_JR
     MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
     return MPX_OK;
 }

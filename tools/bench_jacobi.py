@@ -16,6 +16,10 @@ Prints one JSON line on rank 0 (max time over ranks). With N > 1 ranks the
 final field is gathered and compared bit for bit with ONE device running the
 same warmup + iters iterations from the same initial field ("verified",
 VERDICT r2 #3); a mismatch exits 3.
+
+--rhs: the Poisson sweep (-Laplace(u) = f) with a seeded source term b in
+[-2^-10, 2^-10) — three words per point instead of two — through the same
+transports, with the same N-rank == one-device verification.
 """
 import argparse
 import json
@@ -45,6 +49,7 @@ def main() -> int:
     p.add_argument("--device", default="auto", choices=["auto", "cuda", "cpu"])
     p.add_argument("--graph", action="store_true", help="replay HIP graphs of whole residual cycles")
     p.add_argument("--progress", action="store_true", help="per-phase and per-check timing on stderr")
+    p.add_argument("--rhs", action="store_true", help="Poisson sweep with a seeded right-hand side (off: Laplace)")
     p.add_argument("--no-verify", action="store_true", help="skip the N-rank == one-device comparison")
     p.add_argument("--gpus", type=int, default=None,
                    help="ranks to run (self-launched when no torchrun environment); default WORLD_SIZE or 1")
@@ -70,6 +75,8 @@ def main() -> int:
     say(f"solver ready, transport {sol.transport}")
     sol.set_boundary(top=1.0)
     sol.fill(seed=0)
+    if a.rhs:
+        sol.set_rhs(tensor=rhs_rows(ctx.rank, sol.slab.rows, a.size))
     say("filled")
     sync = (lambda: torch.cuda.synchronize(ctx.device)) if ctx.device.type == "cuda" else (lambda: None)
     if a.progress:
@@ -106,7 +113,8 @@ def main() -> int:
             "n_gpus": ctx.world, "iters": a.iters, "warmup": a.warmup, "grid": [rows, a.size],
             "dtype": "fp32" if a.fp32 else "fp64", "check_every": a.check_every,
             "gpoints_per_s": round(rows * a.size / (ms * 1e-3) / 1e9, 3),
-            "TBps_aggregate": round(2 * rows * a.size * es / (ms * 1e-3) / 1e12, 3),
+            "rhs": bool(a.rhs),
+            "TBps_aggregate": round((3 if a.rhs else 2) * rows * a.size * es / (ms * 1e-3) / 1e12, 3),
             "residual": sol.last_residual,
             "transport": sol.transport,
             "halo": ("one-launch" if sol.peer is not None else "overlap" if sol.overlap else "inorder")
@@ -121,6 +129,12 @@ def main() -> int:
     sol.close()
     parallel.shutdown()
     return 3 if verified is False else 0
+
+
+def rhs_rows(rank: int, nrows: int, cols: int) -> torch.Tensor:
+    """Rank `rank`'s rows of the seeded source term, b in [-2^-10, 2^-10)."""
+    g = torch.Generator(device="cpu").manual_seed(104729 + 7919 * rank)
+    return (torch.rand((nrows, cols), generator=g, dtype=torch.float64) * 2.0 - 1.0) * 2.0 ** -10
 
 
 def one_device_equal(got, sol, rows, a, dt, ctx) -> bool:
@@ -138,6 +152,9 @@ def one_device_equal(got, sol, rows, a, dt, ctx) -> bool:
         parts.append(torch.rand((sr.rows, a.size - 2), generator=g, dtype=torch.float64))
     ref.u[1:1 + rows, 1:-1] = torch.cat(parts).to(ref.u.device).to(dt)
     ref.un.copy_(ref.u)
+    if a.rhs:
+        ref.set_rhs(tensor=torch.cat([rhs_rows(r, Slab(rows, ctx.world, r, 1, 1).rows, a.size)
+                                      for r in range(ctx.world)]))
     ref.run(a.warmup + a.iters)
     same = bool(torch.equal(got.to(ref.u.device), ref.owned))
     del ref
