@@ -94,6 +94,12 @@ _SIGNATURES = {
     "mpx_jacobi_rhs_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "mpx_jacobi_peer_sweep_rhs": (c_int, [c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "mpx_cpu_jacobi_rhs_f64": (ctypes.c_double, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int]),
+    # Chebyshev steps: (u, b or NULL, un in-out, ..., omega, ...)
+    "mpx_jacobi_accel_f64": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.c_double, c_vp, c_vp]),
+    "mpx_jacobi_accel_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.c_double, c_vp, c_vp]),
+    "mpx_jacobi_peer_sweep_accel": (c_int, [c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, ctypes.c_double, c_vp,
+                                            c_vp, c_vp]),
+    "mpx_cpu_jacobi_accel_f64": (ctypes.c_double, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.c_double]),
     "mpx_cpu_threads": (c_int, []),
     "mpx_cpu_vsub_f64": (None, [c_vp, c_vp, c_vp, c_i64]),
     "mpx_cpu_vsub_f32": (None, [c_vp, c_vp, c_vp, c_i64]),
@@ -143,6 +149,9 @@ _TUNE_SIGNATURES = {
     # (u, b, un, cols, pitch, r0, r1, resid, fp64, R, nt, stream)
     "mpx_jacobi_rhs_variant": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
                                        c_vp]),
+    # (u, b or NULL, un in-out, cols, pitch, r0, r1, omega, resid, fp64, R, stream)
+    "mpx_jacobi_accel_variant": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.c_double, c_vp, c_int,
+                                         c_int, c_vp]),
 }
 _tune = None
 

@@ -28,6 +28,13 @@ Every ``check_every`` iterations the sweeps also fold max|u_new - u| into a
 device scalar and one 8-byte all-reduce(MAX) produces the global residual (the
 small-message latency over xGMI is paid once per check, not per iteration).
 
+Chebyshev acceleration (``accel="chebyshev"``): the semi-iterative three-term
+recurrence u_{k+1} = u_{k-1} + omega_{k+1} (J(u_k) - u_{k-1}) over the same
+sweeps (J: the plain or Poisson Jacobi update). The iterate before last is
+what ``un`` holds when a sweep starts, so the sweep reads one more word per
+point and allocates nothing; only u's edge rows cross ranks, as before. The
+iteration count to a fixed tolerance drops from O(N^2) to O(N).
+
 Global boundary: Dirichlet. Row 0 of rank 0's buffer is the top boundary, the
 last buffer row of the last rank the bottom boundary; columns 0 and cols-1 are
 fixed. A decomposed run is bit-identical to a one-rank run.
@@ -36,6 +43,7 @@ fixed. A decomposed run is bit-identical to a one-rank run.
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Callable, Optional
 
 import torch
@@ -55,12 +63,41 @@ class SlabJacobi:
     u <- (((up + down) + (left + right)) + b) / 4, whose fixed point satisfies
     4 u - (sum of the neighbours) = b. The right-hand side is local to each
     rank (never exchanged); a solver that never sets one launches exactly the
-    Laplace sweeps."""
+    Laplace sweeps.
+
+    ``accel="chebyshev"``: Chebyshev (Golub-Varga) acceleration. With k the
+    1-based count of steps since the last (re)start and
+    rho = (cos(pi / (global_rows + 1)) + cos(pi / (cols - 1))) / 2, the Jacobi
+    spectral radius of the grid:
+
+    * k = 1 is the plain sweep (``un``'s contents are ignored; nominal omega 1);
+    * k = 2 uses omega = 1 / (1 - rho^2 / 2);
+    * k >= 3 uses omega_k = 1 / (1 - rho^2 omega_{k-1} / 4);
+
+    and a step k >= 2 writes p + omega (s - p), s the plain step's value and p
+    the iterate before last (``ops.jacobi_sweep(omega=)``). omega is computed
+    in Python floats from k and the global geometry alone, so every rank
+    passes the same bits and a decomposed run stays bit-identical to a
+    one-rank run. ``rho``, ``omega`` (the last one used, None before the first
+    step) and ``accel_step`` (steps since the last (re)start) are attributes.
+    Whatever replaces ``un``'s history restarts the sequence: ``fill``,
+    ``set_boundary``, ``set_rhs``, a halo re-synchronisation after a host
+    write (``_halos_valid = False``), a checkpoint without history, or
+    ``restart_acceleration()``. The residual keeps its meaning, max|s - u|."""
 
     def __init__(self, ctx: DistContext, global_rows: int, cols: int, dtype=torch.float64, check_every: int = 10,
-                 overlap: bool | str = "auto", halo: str = "auto"):
+                 overlap: bool | str = "auto", halo: str = "auto", accel: Optional[str] = None):
         if cols < 3:
             raise ValueError("need at least 3 columns")
+        if accel not in (None, "chebyshev"):
+            raise ValueError(f"unknown acceleration {accel!r} (None or 'chebyshev')")
+        self.accel = accel
+        self.rho: Optional[float] = None
+        if accel is not None:
+            self.rho = 0.5 * (math.cos(math.pi / (global_rows + 1)) + math.cos(math.pi / (cols - 1)))
+        self.omega: Optional[float] = None
+        self.accel_step = 0
+        self._un_is_history = False  # load_checkpoint restored the previous iterate into un
         self.ctx = ctx
         self.cols = cols
         self.dtype = dtype
@@ -119,6 +156,7 @@ class SlabJacobi:
                 t[0, :] = top
             if not self.slab.has_down:
                 t[-1, :] = bottom
+        self.restart_acceleration()
 
     def fill(self, fn: Optional[Callable[[torch.Tensor, torch.Tensor], torch.Tensor]] = None, seed: int = 0) -> None:
         """Interior initial values: fn(global_row_index, col_index) or seeded noise."""
@@ -150,6 +188,7 @@ class SlabJacobi:
             raise ValueError(f"rhs tensor must hold this rank's owned rows, shape {(s.rows, self.cols)}")
         self._quiesce()
         self._graphs.clear()
+        self.restart_acceleration()
         if self.rhs is None:
             self.rhs = torch.zeros((s.buffer_rows, self.cols), dtype=self.dtype, device=self.u.device)
         if tensor is not None:
@@ -170,6 +209,35 @@ class SlabJacobi:
             return "xgmi-peer-signalled"
         return "native-rccl" if self.ctx.native is not None else "torch.distributed"
 
+    def restart_acceleration(self) -> None:
+        """The next step is step 1 of the Chebyshev sequence again: a plain
+        sweep that ignores ``un``. No-op without ``accel``."""
+        self.accel_step = 0
+        self.omega = None
+        self._un_is_history = False
+
+    def _next_omega(self) -> Optional[float]:
+        """omega of the step about to run; None for the plain step (k = 1, or
+        no acceleration). A function of k and the global geometry only."""
+        if self.accel is None or self.accel_step == 0:
+            return None
+        if self.accel_step == 1:
+            return 1.0 / (1.0 - self.rho * self.rho / 2.0)
+        return 1.0 / (1.0 - self.rho * self.rho * self.omega / 4.0)
+
+    def _reset_un(self) -> None:
+        """un <- u before the first sweep after a (re)initialisation (un's fixed
+        rows and columns are never swept). That loses the previous iterate, so
+        the Chebyshev sequence restarts, unless load_checkpoint has just put
+        the previous iterate there: then only the halo rows are refreshed."""
+        if self._un_is_history:
+            self.un[0].copy_(self.u[0])
+            self.un[-1].copy_(self.u[-1])
+            self._un_is_history = False
+            return
+        self.un.copy_(self.u)
+        self.restart_acceleration()
+
     def _quiesce(self) -> None:
         """Peer mode, before any host write to the IPC-shared buffers: every
         rank's queued sweeps have finished (a neighbour's last untracked sweep
@@ -188,13 +256,13 @@ class SlabJacobi:
             if self.peer is not None:
                 self._quiesce()
                 self._graphs.clear()
-            self.un.copy_(self.u)
+            self._reset_un()
             if self.peer is not None:
                 self.peer.publish(self.u, self.iteration)
             self._halos_valid = True
             return
         self.halo.exchange(self.u)
-        self.un.copy_(self.u)
+        self._reset_un()
         self._halos_valid = True
 
     def check_peer(self) -> None:
@@ -207,13 +275,13 @@ class SlabJacobi:
         return self.u[1:1 + self.slab.rows]
 
     # ------------------------------------------------------------------ stepping
-    def _sweep(self, r0: int, r1: int, track: bool) -> None:
+    def _sweep(self, r0: int, r1: int, track: bool, omega: Optional[float] = None) -> None:
         if r1 <= r0:
             return
         if self.u.is_cuda:
-            ops.jacobi_sweep(self.u, self.un, r0, r1, self.resid if track else None, rhs=self.rhs)
+            ops.jacobi_sweep(self.u, self.un, r0, r1, self.resid if track else None, rhs=self.rhs, omega=omega)
         else:
-            r = ops.jacobi_sweep(self.u, self.un, r0, r1, rhs=self.rhs)
+            r = ops.jacobi_sweep(self.u, self.un, r0, r1, rhs=self.rhs, omega=omega)
             if track:
                 self.resid.fill_(max(float(self.resid.item()), r))
 
@@ -248,10 +316,17 @@ class SlabJacobi:
         n = s.rows
         if track:
             self.resid.zero_()
+        w = self._next_omega()  # None: the plain sweeps, exactly as without accel
         if self.peer is not None:
             from .. import _native
 
-            if self.rhs is not None:  # b is local: same descriptor, same counters
+            if w is not None:  # p is local too: same descriptor, same counters
+                _native.check(_native.lib().mpx_jacobi_peer_sweep_accel(
+                    int(self.dtype == torch.float64), self.u.data_ptr(),
+                    None if self.rhs is None else self.rhs.data_ptr(), self.un.data_ptr(), self.cols, self.cols, n, w,
+                    self.resid.data_ptr() if track else None, ctypes.byref(self.peer.desc),
+                    _native.stream_of(self.u)))
+            elif self.rhs is not None:  # b is local: same descriptor, same counters
                 _native.check(_native.lib().mpx_jacobi_peer_sweep_rhs(
                     int(self.dtype == torch.float64), self.u.data_ptr(), self.rhs.data_ptr(), self.un.data_ptr(),
                     self.cols, self.cols, n, self.resid.data_ptr() if track else None,
@@ -264,16 +339,19 @@ class SlabJacobi:
         elif self.ctx.is_distributed and self.overlap:
             edge = [1] if n == 1 else [1, n]
             for r in edge:
-                self._sweep(r, r + 1, track)
+                self._sweep(r, r + 1, track, w)
             self.halo.start(self.un)      # RCCL waits for the edge rows only
-            self._sweep(2, n, track)      # interior overlaps the transfer
+            self._sweep(2, n, track, w)   # interior overlaps the transfer (same omega)
             self.halo.wait()
         else:
-            self._sweep(1, n + 1, track)
+            self._sweep(1, n + 1, track, w)
             if not self.no_halo:
                 self.halo.exchange(self.un)
         self.u, self.un = self.un, self.u
         self.iteration += 1
+        if self.accel is not None:
+            self.omega = 1.0 if w is None else w
+            self.accel_step += 1
         if track:
             all_reduce_max(self.resid, self.ctx)
 
@@ -285,9 +363,13 @@ class SlabJacobi:
         count so u/un are back in place at the end of every replay — with the
         host reading the residual once per replay. Launch-bound sweeps (small
         slabs, many ranks) no longer wait on the host's per-launch cost.
-        Falls back to eager steps when the step cannot be captured."""
+        Falls back to eager steps when the step cannot be captured.
+
+        With ``accel`` the steps always run eagerly: omega is a by-value kernel
+        argument that changes every iteration, so a replayed cycle would carry
+        stale values. ``graph=True`` is accepted and captures nothing."""
         done = 0
-        if graph and self.u.is_cuda:
+        if graph and self.u.is_cuda and self.accel is None:
             done = self._run_graph(iters, tol)
             if done < 0:  # tolerance reached inside the graphed part
                 return self.iteration
@@ -351,12 +433,20 @@ class SlabJacobi:
 
     def save_checkpoint(self, prefix: str) -> str:
         """One file per rank: owned rows (+ halos), iteration, residual and,
-        when one is set, the right-hand side."""
+        when one is set, the right-hand side. An accelerated solver also stores
+        the previous iterate (``u_prev``) and ``accel`` = {step, omega, rho}, so
+        a resumed run continues the Chebyshev sequence bit for bit."""
         path = f"{prefix}.rank{self.ctx.rank}.pt"
         ck = {"u": self.u.cpu(), "iteration": self.iteration, "residual": self.last_residual,
               "global_rows": self.slab.global_rows, "world": self.ctx.world, "cols": self.cols}
         if self.rhs is not None:
             ck["rhs"] = self.rhs.cpu()
+        if self.accel is not None:
+            # a pending re-synchronisation restarts the sequence anyway
+            live = self._halos_valid and self.accel_step > 0
+            ck["u_prev"] = self.un.cpu()
+            ck["accel"] = {"step": self.accel_step if live else 0, "omega": self.omega if live else None,
+                           "rho": self.rho}
         torch.save(ck, path)
         return path
 
@@ -382,3 +472,10 @@ class SlabJacobi:
         self.iteration = int(ck["iteration"])
         self.last_residual = ck["residual"]
         self._halos_valid = False
+        self.restart_acceleration()  # checkpoints without history load as a restart
+        if self.accel is not None and "u_prev" in ck and "accel" in ck and int(ck["accel"]["step"]) > 0:
+            # sync_halos must not clobber the previous iterate in un's owned rows
+            self.un.copy_(ck["u_prev"].to(self.u.device, self.dtype))
+            self.accel_step = int(ck["accel"]["step"])
+            self.omega = float(ck["accel"]["omega"])
+            self._un_is_history = True

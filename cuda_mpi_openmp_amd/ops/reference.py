@@ -105,13 +105,20 @@ def classify(img: torch.Tensor, mu: np.ndarray, inv: np.ndarray, device=None) ->
 
 
 def jacobi(u: torch.Tensor, r0: int, r1: int, keep_dtype: bool = False,
-           rhs: torch.Tensor | None = None) -> torch.Tensor:
+           rhs: torch.Tensor | None = None, omega: float | None = None,
+           prev: torch.Tensor | None = None) -> torch.Tensor:
     """One sweep over rows [r0, r1) (1-based, halo rows at 0 and rows+1), in
     fp64, or with ``keep_dtype`` in u's own dtype: three correctly rounded adds
     in the kernels' association and an exact scale, so the native result must
     equal it bit for bit. ``rhs`` (u's shape; b = h^2 f of -Laplace(u) = f) is
     a fourth correctly rounded add after the neighbours:
-    (((up + down) + (left + right)) + b) * 0.25."""
+    (((up + down) + (left + right)) + b) * 0.25.
+
+    ``omega`` with ``prev`` (u's shape: the iterate before u): the Chebyshev
+    step prev + omega * (s - prev) at the interior points of rows [r0, r1),
+    with s the value above and omega rounded once to the working dtype: a
+    subtract, a multiply and an add, each rounded. Every other element of the
+    result is u's, as without omega."""
     u = u.cpu() if keep_dtype else u.cpu().to(torch.float64)
     un = u.clone()
     c = u[r0:r1, 1:-1]
@@ -122,6 +129,14 @@ def jacobi(u: torch.Tensor, r0: int, r1: int, keep_dtype: bool = False,
             raise ValueError("rhs must have u's shape")
         s = s + b[r0:r1, 1:-1]
     s = s * 0.25
+    if (omega is None) != (prev is None):
+        raise ValueError("omega and prev come together")
+    if omega is not None:
+        p = prev.cpu().to(u.dtype)
+        if p.shape != u.shape:
+            raise ValueError("prev must have u's shape")
+        p = p[r0:r1, 1:-1]
+        s = p + torch.tensor(omega, dtype=u.dtype) * (s - p)
     un[r0:r1, 1:-1] = s
     del c
     return un

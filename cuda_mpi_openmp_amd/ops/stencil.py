@@ -8,6 +8,7 @@ Layout: ``u`` has shape (rows + 2, cols); row 0 and row rows+1 are halo rows
 
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
@@ -16,13 +17,24 @@ from .. import _native
 
 
 def jacobi_sweep(u: torch.Tensor, un: torch.Tensor, r0: int, r1: int,
-                 resid: Optional[torch.Tensor] = None, rhs: Optional[torch.Tensor] = None) -> Optional[float]:
+                 resid: Optional[torch.Tensor] = None, rhs: Optional[torch.Tensor] = None,
+                 omega: Optional[float] = None) -> Optional[float]:
     """GPU: enqueue the sweep (resid, a 1-element tensor zeroed by the caller,
     accumulates the max on device). CPU: run it and return the residual.
 
     ``rhs`` (u's shape, dtype and device, contiguous): the Poisson sweep
     un = (((up + down) + (left + right)) + rhs) * 0.25 for -Laplace(u) = f with
-    rhs = h^2 f; read at the interior points of rows [r0, r1) only."""
+    rhs = h^2 f; read at the interior points of rows [r0, r1) only.
+
+    ``omega`` (a finite, positive float): the Chebyshev step. ``un`` is in-out:
+    on entry rows [r0, r1) hold the iterate before ``u``, p, and the sweep writes
+    p + omega * (s - p) with s the plain or Poisson value (three rounded
+    operations, omega rounded once to u's dtype). The residual stays
+    max|s - u|. Without omega the call launches the plain sweeps."""
+    if omega is not None:
+        omega = float(omega)
+        if not (math.isfinite(omega) and omega > 0.0):
+            raise ValueError("omega must be finite and positive")
     if u.shape != un.shape or u.dim() != 2 or u.dtype != un.dtype:
         raise ValueError("u/un must be matching 2-D tensors")
     if not (u.is_contiguous() and un.is_contiguous()):
@@ -42,7 +54,11 @@ def jacobi_sweep(u: torch.Tensor, un: torch.Tensor, r0: int, r1: int,
             raise ValueError("resid must match u's dtype and device")
         if u.dtype not in (torch.float64, torch.float32):
             raise ValueError("jacobi supports float64/float32")
-        if rhs is not None:
+        if omega is not None:
+            fn = L.mpx_jacobi_accel_f64 if u.dtype == torch.float64 else L.mpx_jacobi_accel_f32
+            _native.check(fn(u.data_ptr(), None if rhs is None else rhs.data_ptr(), un.data_ptr(), cols, cols, r0, r1,
+                             omega, rp, _native.stream_of(u)))
+        elif rhs is not None:
             fn = L.mpx_jacobi_rhs_f64 if u.dtype == torch.float64 else L.mpx_jacobi_rhs_f32
             _native.check(fn(u.data_ptr(), rhs.data_ptr(), un.data_ptr(), cols, cols, r0, r1, rp, _native.stream_of(u)))
         elif u.dtype == torch.float64:
@@ -54,7 +70,10 @@ def jacobi_sweep(u: torch.Tensor, un: torch.Tensor, r0: int, r1: int,
         return None
     if u.dtype != torch.float64:
         raise ValueError("CPU jacobi reference is float64")
-    if rhs is not None:
+    if omega is not None:
+        r = L.mpx_cpu_jacobi_accel_f64(u.data_ptr(), None if rhs is None else rhs.data_ptr(), un.data_ptr(), cols, cols,
+                                       r0, r1, omega)
+    elif rhs is not None:
         r = L.mpx_cpu_jacobi_rhs_f64(u.data_ptr(), rhs.data_ptr(), un.data_ptr(), cols, cols, r0, r1)
     else:
         r = L.mpx_cpu_jacobi_f64(u.data_ptr(), un.data_ptr(), cols, cols, r0, r1)

@@ -320,6 +320,25 @@ int mpx_jacobi_rhs_f32(const float *u, const float *b, float *un, int cols, int 
                        float *resid, void *stream);
 int mpx_jacobi_peer_sweep_rhs(int fp64, void *u, const void *b, void *un, int cols, int pitch, int rows,
                               void *resid, const mpx_jacobi_peer *p, void *stream);
+/* Chebyshev (semi-iterative) step. With s the value of the plain sweep (b NULL)
+ * or of the Poisson sweep (b given) and p = un[i][j] as found on entry, the
+ * iterate before last:
+ *   un[i][j] = p + omega * (s - p)
+ * a subtract, a multiply and an add, each rounded separately (never an FMA), so
+ * fp32, fp64, the CPU reference and a plain expression agree bit for bit. un is
+ * in-out: only rows [r0, r1) are read and written. omega is rounded once to the
+ * sweep's type; it must be finite and positive (also after that rounding).
+ * The residual word keeps its meaning, max|s - u|, a quarter of the defect's
+ * max norm, independent of omega. Path selection, the alignment rules and the
+ * peer descriptor are those of the sweeps above. The first step of a sequence
+ * is the plain sweep itself (mpx_jacobi_f64 / mpx_jacobi_rhs_f64), not
+ * omega = 1: (s - p) + p is not s in floating point. */
+int mpx_jacobi_accel_f64(const double *u, const double *b, double *un, int cols, int pitch, int r0, int r1,
+                         double omega, double *resid, void *stream);
+int mpx_jacobi_accel_f32(const float *u, const float *b, float *un, int cols, int pitch, int r0, int r1,
+                         double omega, float *resid, void *stream);
+int mpx_jacobi_peer_sweep_accel(int fp64, void *u, const void *b, void *un, int cols, int pitch, int rows,
+                                double omega, void *resid, const mpx_jacobi_peer *p, void *stream);
 
 /* ---------------- lab5: ascending sort (no reference program) ---------------- */
 /* In place on the device; dtype is an mpx_sort_dtype. int32/float32: LSD radix sort
@@ -372,6 +391,10 @@ void mpx_cpu_classify(uint32_t *img, int64_t npix, int nc, const double *mu, con
 double mpx_cpu_jacobi_f64(const double *u, double *un, int cols, int pitch, int r0, int r1);
 /* with the right-hand side of mpx_jacobi_rhs_f64; NaN when b is NULL */
 double mpx_cpu_jacobi_rhs_f64(const double *u, const double *b, double *un, int cols, int pitch, int r0, int r1);
+/* the Chebyshev step of mpx_jacobi_accel_f64 (b may be NULL, un is in-out);
+ * NaN, with nothing written, on a null u / un, bad geometry or a bad omega */
+double mpx_cpu_jacobi_accel_f64(const double *u, const double *b, double *un, int cols, int pitch, int r0, int r1,
+                                double omega);
 void mpx_cpu_sort(void *data, int64_t n, int dtype);
 void mpx_cpu_sort_pairs(void *keys, uint32_t *vals, int64_t n, int dtype, int flags);
 

@@ -2,7 +2,8 @@
  * not by libmpx.so and not part of the production C API in capi.h. Declared
  * here for the sort (native/tune/sort_variants.hip, kernels shared with the
  * production sort through src/kernels/sort_radix.hpp); the conv, Jacobi and
- * vsub variants (mpx_conv_variant, mpx_jacobi_variant, mpx_jacobi_rhs_variant, mpx_vsub_variant) are
+ * vsub variants (mpx_conv_variant, mpx_jacobi_variant, mpx_jacobi_rhs_variant, mpx_jacobi_accel_variant,
+ * mpx_vsub_variant) are
  * bound by name from Python (_native.tune_lib). Used by
  * tools/experiments/{lab5_bench,sort_probe,jbench,vsub_sweep}.py, tools/kbench.py
  * and the GPU suites. */

@@ -424,6 +424,38 @@ double mpx_cpu_jacobi_rhs_f64(const double *u, const double *b, double *un, int 
     return res;
 }
 
+/* Chebyshev step: un = un + omega * (s - un) with s the plain (b == NULL) or
+ * Poisson value above; a subtract, a multiply and an add, each rounded
+ * (-ffp-contract=off), as in the GPU kernels. un is in-out; the residual stays
+ * max|s - u|. NaN, with nothing written, on a null u / un, bad geometry or an
+ * omega that is not finite and positive. */
+double mpx_cpu_jacobi_accel_f64(const double *u, const double *b, double *un, int cols, int pitch, int r0, int r1,
+                                double omega) {
+    double res = 0.0;
+    int i;
+    if (!u || !un || cols < 1 || pitch < cols || r0 < 1 || r1 < r0 || !(omega > 0.0) || !isfinite(omega)) return NAN;
+#pragma omp parallel for schedule(static) reduction(max : res)
+    for (i = r0; i < r1; ++i) {
+        const double *up = u + (int64_t)(i - 1) * pitch;
+        const double *uc = u + (int64_t)i * pitch;
+        const double *ud = u + (int64_t)(i + 1) * pitch;
+        const double *bc = b ? b + (int64_t)i * pitch : NULL;
+        double *o = un + (int64_t)i * pitch;
+        o[0] = uc[0];
+        o[cols - 1] = uc[cols - 1];
+        for (int j = 1; j < cols - 1; ++j) {
+            const double n4 = (up[j] + ud[j]) + (uc[j - 1] + uc[j + 1]);
+            const double s = bc ? (n4 + bc[j]) * 0.25 : n4 * 0.25;
+            const double d = fabs(s - uc[j]);
+            res = d > res ? d : res;
+            const double p = o[j];
+            const double t = omega * (s - p);
+            o[j] = p + t;
+        }
+    }
+    return res;
+}
+
 /* Host statistics with the reference's exact operation order
  * (reference lab3/src/main.cu:102-152): mean, unbiased covariance, cofactor
  * determinant and the modular-index adjugate inverse. */

@@ -28,6 +28,8 @@ void mpx_cpu_conv(const uint32_t *in, uint32_t *out, int w, int pitch, int oy0, 
 void mpx_cpu_classify(uint32_t *img, int64_t npix, int nc, const double *mu, const double *inv);
 double mpx_cpu_jacobi_f64(const double *u, double *un, int cols, int pitch, int r0, int r1);
 double mpx_cpu_jacobi_rhs_f64(const double *u, const double *b, double *un, int cols, int pitch, int r0, int r1);
+double mpx_cpu_jacobi_accel_f64(const double *u, const double *b, double *un, int cols, int pitch, int r0, int r1,
+                                double omega);
 /* lab5: ascending sort in place, same order as mpx_sort (dtype: enum mpx_sort_dtype). */
 void mpx_cpu_sort(void *data, int64_t n, int dtype);
 /* Stable key-value sort, same order and flags as mpx_sort_pairs_ws (capi.h:

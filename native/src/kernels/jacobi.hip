@@ -21,16 +21,24 @@
 // generic per-lane kernel below.
 #include "jacobi_wave.hpp"
 
+#include <limits>
+
 namespace mpx {
 namespace {
 
 // RHS: the Poisson sweep (((up + dn) + (l + r)) + b) * 0.25 with the source
 // term b laid out like u; same path selection, b's alignment included
-template <typename T, bool RHS = false>
+// ACCEL: the Chebyshev step un = un + omega * (s - un) (jacobi_wave.hpp), un
+// in-out; omega arrives as a double and is rounded to T once, here
+template <typename T, bool RHS = false, bool ACCEL = false>
 int launch_jacobi(const T *u, T *un, int cols, int pitch, int r0, int r1, T *resid, void *stream,
-                  const T *b = nullptr) {
+                  const T *b = nullptr, double omega_d = 1.0) {
     MPX_CHECK_ARG(u && un && (!RHS || b), "null pointer");
     MPX_CHECK_ARG(cols >= 1 && pitch >= cols && r0 >= 1 && r1 >= r0, "bad slab geometry");
+    // in T's range before the conversion (NaN fails the first comparison), positive after it
+    const bool w_ok = omega_d > 0.0 && omega_d <= (double)std::numeric_limits<T>::max();
+    const T omega = w_ok ? (T)omega_d : (T)0;
+    MPX_CHECK_ARG(!ACCEL || omega > (T)0, "omega must be finite and positive");
     if (r1 == r0) return MPX_OK;
     constexpr int NV = JVec<T>::n;
     const bool al16 = aligned16(u) && aligned16(un) && (!RHS || aligned16(b));
@@ -46,9 +54,9 @@ int launch_jacobi(const T *u, T *un, int cols, int pitch, int r0, int r1, T *res
         int R = kJacobiRows;
         while (R > 1 && (int64_t)strips * ((rows + R - 1) / R) < 16384) R >>= 1;
         const int nwaves = strips * ((rows + R - 1) / R);
-        hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 0, true, false, true, 4, RHS, RHS && kRhsNT>),
+        hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 0, true, false, true, 4, RHS, RHS && kRhsNT, ACCEL>),
                            dim3((nwaves + 3) / 4), dim3(256), 0, as_stream(stream), u, un, cols, pitch, r0, r1, strips, R, nwaves, resid,
-                           mpx_jacobi_peer{}, b);
+                           mpx_jacobi_peer{}, b, omega);
         MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
         return MPX_OK;
     }
@@ -57,20 +65,24 @@ int launch_jacobi(const T *u, T *un, int cols, int pitch, int r0, int r1, T *res
     const dim3 blk(256);
     const dim3 grd((lanes + 255) / 256, (r1 - r0 + kRows - 1) / kRows);
     if (vec)
-        hipLaunchKernelGGL((jacobi_kernel<T, true, RHS>), grd, blk, 0, as_stream(stream), u, un, cols, pitch, r0, r1,
-                           resid, b);
+        hipLaunchKernelGGL((jacobi_kernel<T, true, RHS, ACCEL>), grd, blk, 0, as_stream(stream), u, un, cols, pitch,
+                           r0, r1, resid, b, omega);
     else
-        hipLaunchKernelGGL((jacobi_kernel<T, false, RHS>), grd, blk, 0, as_stream(stream), u, un, cols, pitch, r0, r1,
-                           resid, b);
+        hipLaunchKernelGGL((jacobi_kernel<T, false, RHS, ACCEL>), grd, blk, 0, as_stream(stream), u, un, cols, pitch,
+                           r0, r1, resid, b, omega);
     MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
     return MPX_OK;
 }
 
-template <typename T, bool RHS = false>
+template <typename T, bool RHS = false, bool ACCEL = false>
 int launch_jacobi_peer(const T *u, T *un, int cols, int pitch, int rows, T *resid, const mpx_jacobi_peer &pr,
-                       void *stream, const T *b = nullptr) {
+                       void *stream, const T *b = nullptr, double omega_d = 1.0) {
     MPX_CHECK_ARG(u && un && pr.sync && (!RHS || b), "null pointer");
     MPX_CHECK_ARG(cols >= 1 && pitch >= cols && rows >= 1, "bad slab geometry");
+    // in T's range before the conversion (NaN fails the first comparison), positive after it
+    const bool w_ok = omega_d > 0.0 && omega_d <= (double)std::numeric_limits<T>::max();
+    const T omega = w_ok ? (T)omega_d : (T)0;
+    MPX_CHECK_ARG(!ACCEL || omega > (T)0, "omega must be finite and positive");
     MPX_CHECK_ARG(!pr.up_flag == !pr.up_row[0] && !pr.up_row[0] == !pr.up_row[1], "up neighbour: rows and flag together");
     MPX_CHECK_ARG(!pr.dn_flag == !pr.dn_row[0] && !pr.dn_row[0] == !pr.dn_row[1], "down neighbour: rows and flag together");
     constexpr int NV = JVec<T>::n;
@@ -88,8 +100,9 @@ int launch_jacobi_peer(const T *u, T *un, int cols, int pitch, int rows, T *resi
     int R = kJacobiRows;
     while (R > 1 && (int64_t)strips * ((rows + R - 1) / R) < 16384) R >>= 1;
     const int nwaves = strips * ((rows + R - 1) / R);
-    hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 0, true, true, true, 4, RHS, RHS && kRhsNT>), dim3((nwaves + 3) / 4),
-                       dim3(256), 0, as_stream(stream), u, un, cols, pitch, 1, rows + 1, strips, R, nwaves, resid, pr, b);
+    hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 0, true, true, true, 4, RHS, RHS && kRhsNT, ACCEL>),
+                       dim3((nwaves + 3) / 4), dim3(256), 0, as_stream(stream), u, un, cols, pitch, 1, rows + 1, strips, R,
+                       nwaves, resid, pr, b, omega);
     MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
     return MPX_OK;
 }
@@ -138,6 +151,37 @@ extern "C" int mpx_jacobi_peer_sweep_rhs(int fp64, void *u, const void *b, void 
                                                 stream, (const double *)b);
     return launch_jacobi_peer<float, true>((const float *)u, (float *)un, cols, pitch, rows, (float *)resid, *p, stream,
                                            (const float *)b);
+}
+
+// Chebyshev-accelerated sweeps: b is nullable (null = the Laplace form)
+extern "C" int mpx_jacobi_accel_f64(const double *u, const double *b, double *un, int cols, int pitch, int r0, int r1,
+                                    double omega, double *resid, void *stream) {
+    if (b) return mpx::launch_jacobi<double, true, true>(u, un, cols, pitch, r0, r1, resid, stream, b, omega);
+    return mpx::launch_jacobi<double, false, true>(u, un, cols, pitch, r0, r1, resid, stream, nullptr, omega);
+}
+
+extern "C" int mpx_jacobi_accel_f32(const float *u, const float *b, float *un, int cols, int pitch, int r0, int r1,
+                                    double omega, float *resid, void *stream) {
+    if (b) return mpx::launch_jacobi<float, true, true>(u, un, cols, pitch, r0, r1, resid, stream, b, omega);
+    return mpx::launch_jacobi<float, false, true>(u, un, cols, pitch, r0, r1, resid, stream, nullptr, omega);
+}
+
+extern "C" int mpx_jacobi_peer_sweep_accel(int fp64, void *u, const void *b, void *un, int cols, int pitch, int rows,
+                                           double omega, void *resid, const mpx_jacobi_peer *p, void *stream) {
+    using namespace mpx;
+    MPX_CHECK_ARG(p, "null peer descriptor");
+    if (fp64) {
+        if (b)
+            return launch_jacobi_peer<double, true, true>((const double *)u, (double *)un, cols, pitch, rows,
+                                                          (double *)resid, *p, stream, (const double *)b, omega);
+        return launch_jacobi_peer<double, false, true>((const double *)u, (double *)un, cols, pitch, rows,
+                                                       (double *)resid, *p, stream, nullptr, omega);
+    }
+    if (b)
+        return launch_jacobi_peer<float, true, true>((const float *)u, (float *)un, cols, pitch, rows, (float *)resid,
+                                                     *p, stream, (const float *)b, omega);
+    return launch_jacobi_peer<float, false, true>((const float *)u, (float *)un, cols, pitch, rows, (float *)resid, *p,
+                                                  stream, nullptr, omega);
 }
 
 extern "C" int mpx_jacobi_sync_bytes(void) { return 4 * 128; }

@@ -44,10 +44,16 @@ __device__ __forceinline__ T lane_of(const typename JVec<T>::type &v, int i) {
 // RHS: Poisson source term b (laid out like u, already scaled by h^2), added
 // after the four neighbours: (((up + dn) + (l + r)) + b) * 0.25. b is read at
 // interior points of the swept rows only; RHS = false never touches it.
-template <typename T, bool VEC, bool RHS = false>
+// ACCEL: Chebyshev (semi-iterative) step. With s the value above and p the
+// iterate before last, found in un on entry, the output is p + omega * (s - p):
+// a subtract, a multiply and an add, each rounded (never an FMA). In place is
+// safe here because a lane loads exactly the elements of un it stores, each
+// before its store. The residual stays max|s - u|. ACCEL = false never reads
+// un or omega.
+template <typename T, bool VEC, bool RHS = false, bool ACCEL = false>
 __global__ __launch_bounds__(256) void jacobi_kernel(const T *__restrict__ u, T *__restrict__ un, int cols,
                                                      int pitch, int r0, int r1, T *__restrict__ resid,
-                                                     const T *__restrict__ b) {
+                                                     const T *__restrict__ b, T omega) {
     using V = typename JVec<T>::type;
     constexpr int NV = VEC ? JVec<T>::n : 1;
     const int j0 = NV * (blockIdx.x * blockDim.x + threadIdx.x);
@@ -94,6 +100,23 @@ __global__ __launch_bounds__(256) void jacobi_kernel(const T *__restrict__ u, T 
                     for (int k = 0; k < NV; ++k) src[k] = (j0 + k < cols) ? brow[j0 + k] : (T)0;
                 }
             }
+            T prev[NV];
+            if constexpr (ACCEL) {  // this lane's own elements of un's row i, before they are stored
+                const T *prow = un + (int64_t)i * pitch;
+                bool loaded = false;
+                if constexpr (VEC) {
+                    if (j0 + NV <= cols) {
+                        const V q = *reinterpret_cast<const V *>(prow + j0);
+#pragma unroll
+                        for (int k = 0; k < NV; ++k) prev[k] = lane_of<T>(q, k);
+                        loaded = true;
+                    }
+                }
+                if (!loaded) {
+#pragma unroll
+                    for (int k = 0; k < NV; ++k) prev[k] = (j0 + k < cols) ? prow[j0 + k] : (T)0;
+                }
+            }
 #pragma unroll
             for (int k = 0; k < NV; ++k) {
                 const int j = j0 + k;
@@ -103,7 +126,13 @@ __global__ __launch_bounds__(256) void jacobi_kernel(const T *__restrict__ u, T 
                 if constexpr (RHS) s = (((up[k] + dn[k]) + (l + r)) + src[k]) * (T)0.25;
                 else s = ((up[k] + dn[k]) + (l + r)) * (T)0.25;
                 const bool interior = j > 0 && j < cols - 1;
-                res[k] = interior ? s : cen[k];
+                if constexpr (ACCEL) {
+                    const T d = s - prev[k];
+                    const T t = omega * d;
+                    res[k] = interior ? prev[k] + t : cen[k];
+                } else {
+                    res[k] = interior ? s : cen[k];
+                }
                 if (interior && j < cols) {
                     const T d = s > cen[k] ? s - cen[k] : cen[k] - s;
                     rmax = d > rmax ? d : rmax;
@@ -153,6 +182,10 @@ constexpr uint32_t kDrop = 0x7ffffff0u;   // buffer offset past any range: store
 // and shared with no other row block; 16384^2, same process, interleaved rounds
 // (profiles/jacobi.md): fp64 1142 us vs 1187 plain, fp32 548 vs 557
 constexpr bool kRhsNT = true;
+// rows by which the loads of the previous iterate p (ACCEL) run ahead of their
+// use, 1..3: 3 is the lead of the u and b rings (four live slots); 1 and 2 keep
+// fewer registers live and were measured against it (profiles/jacobi.md)
+constexpr int kAccelLead = 3;
 
 template <typename T> struct JWide;
 template <> struct JWide<double> { typedef double type __attribute__((ext_vector_type(2))); };
@@ -250,12 +283,31 @@ __device__ __forceinline__ T wave_max_dpp(T v) {
 // (u's to [i0 - 1, i1]) and slot 0 has no prologue load: b is read once per
 // sweep, halo rows and all of b outside [r0, r1) never. BNT: those loads
 // non-temporal (tuning A/B). b is purely local, also with PEER.
+// ACCEL: Chebyshev step out = p + omega * (s - p), three rounded operations,
+// with p the iterate before last, which is what un holds on entry. p rides in
+// a third ring indexed and clamped like B and is read through un itself with
+// non-temporal loads (read once, then overwritten). Updating un in place is
+// safe because
+//   * a wave reads un only at rows [i0, i1 - 1] of its own block, and its
+//     output lanes only at the columns they store: no other wave writes them;
+//   * every row's load precedes that row's store in program order (the store's
+//     value depends on the load), and the hardware keeps a wave's accesses to
+//     one address in order;
+//   * the clamped duplicate loads all name row i1 - 1 (i0 walking up), the row
+//     stored last in the walk direction, and are issued before its store or
+//     feed no step that stores;
+//   * lanes 0 and 63 (columns of the neighbouring strips) and the surplus steps
+//     of a TAIL_EXIT = false form may read stale or in-flight values; those
+//     reach no store (offset kDrop) and no residual (which never uses p).
+// p is purely local, also with PEER: the neighbours read u's edge rows or the
+// mailbox copies, never un's previous contents. ACCEL = false never reads un
+// or omega.
 template <typename T, int AUX = 0, int LNT = 0, bool TAIL_EXIT = true, bool PEER = false, bool ALT = false,
-          int WPB = 4, bool RHS = false, bool BNT = false>
+          int WPB = 4, bool RHS = false, bool BNT = false, bool ACCEL = false>
 __global__ __launch_bounds__(64 * WPB) void jacobi_wave_kernel(const T *__restrict__ u, T *__restrict__ un, int cols,
                                                           int pitch, int r0, int r1, int strips, int rows_per_wave,
                                                           int nwaves, T *__restrict__ resid, mpx_jacobi_peer pr,
-                                                          const T *__restrict__ b) {
+                                                          const T *__restrict__ b, T omega) {
     using V = typename JWide<T>::type;
     constexpr int NV = JVec<T>::n;
     const int lane = threadIdx.x & 63;
@@ -320,6 +372,10 @@ __global__ __launch_bounds__(64 * WPB) void jacobi_wave_kernel(const T *__restri
             if constexpr (BNT) return __builtin_nontemporal_load(p);
             return *p;
         };
+        auto ldp = [&](int i) {
+            return __builtin_nontemporal_load(
+                reinterpret_cast<const V *>(un + (int64_t)cvc * NV + (int64_t)i * pitch));
+        };
         const uint32_t soff = out_lane ? (uint32_t)(cv * NV * sizeof(T)) : kDrop;
         const int j0 = cv * NV;
         // One walk over the block's rows, prologue included (each direction its
@@ -359,6 +415,15 @@ __global__ __launch_bounds__(64 * WPB) void jacobi_wave_kernel(const T *__restri
                 }
                 B[4] = V{};
             }
+            V P[ACCEL ? 5 : 1];
+            if constexpr (ACCEL) {
+                static_assert(kAccelLead >= 1 && kAccelLead <= 3, "the ring has five slots");
+                P[0] = V{};
+                P[1] = UPW ? ldp(i1 - 1) : ldp(i0);
+                P[2] = kAccelLead < 2 ? V{} : UPW ? ldp(max(i1 - 2, i0)) : ldp(min(i0 + 1, i1 - 1));
+                P[3] = kAccelLead < 3 ? V{} : UPW ? ldp(max(i1 - 3, i0)) : ldp(min(i0 + 2, i1 - 1));
+                P[4] = V{};
+            }
             __builtin_amdgcn_sched_barrier(0);
             auto step = [&](auto kc, int i) {
                 constexpr int k = decltype(kc)::value;
@@ -366,6 +431,8 @@ __global__ __launch_bounds__(64 * WPB) void jacobi_wave_kernel(const T *__restri
                 // x_{r+3} replaces x_{r-2} (walking up: x_{r-3} replaces x_{r+2})
                 S[(k + 4) % 5] = UPW ? ld(max(r - 3, i0 - 1)) : ld(min(r + 3, i1));
                 if constexpr (RHS) B[(k + 4) % 5] = UPW ? ldb(max(r - 3, i0)) : ldb(min(r + 3, i1 - 1));
+                if constexpr (ACCEL)
+                    P[(k + 1 + kAccelLead) % 5] = UPW ? ldp(max(r - kAccelLead, i0)) : ldp(min(r + kAccelLead, i1 - 1));
                 const V up = S[(UPW ? k + 2 : k) % 5], cen = S[(k + 1) % 5], dn = S[(UPW ? k : k + 2) % 5];
                 const T left = dpp_shift<T>(cen[NV - 1], 0x138);  // lane - 1's last element
                 const T right = dpp_shift<T>(cen[0], 0x130);      // lane + 1's first element
@@ -385,7 +452,14 @@ __global__ __launch_bounds__(64 * WPB) void jacobi_wave_kernel(const T *__restri
                     if constexpr (RHS) sm = (((up[e] + dn[e]) + (l + rr)) + B[(k + 1) % 5][e]) * (T)0.25;
                     else sm = ((up[e] + dn[e]) + (l + rr)) * (T)0.25;
                     const bool interior = j > 0 && j < cols - 1;
-                    res[e] = interior ? sm : cen[e];
+                    if constexpr (ACCEL) {
+                        const T pv = P[(k + 1) % 5][e];
+                        const T df = sm - pv;
+                        const T t = omega * df;
+                        res[e] = interior ? pv + t : cen[e];
+                    } else {
+                        res[e] = interior ? sm : cen[e];
+                    }
                     const T d = sm > cen[e] ? sm - cen[e] : cen[e] - sm;
                     rmax = fmax(rmax, (interior && counted) ? d : (T)0);  // select + v_max: no exec branch
                 }

@@ -23,23 +23,23 @@ extern "C" int mpx_jacobi_variant(void *u, void *un, int cols, int pitch, int r0
     hipStream_t s = as_stream(stream);
 #define MPX_JV(T, A)                                                                                          \
     hipLaunchKernelGGL((jacobi_wave_kernel<T, A>), g, b, 0, s, (const T *)u, (T *)un, cols, pitch, r0, r1, strips, \
-                       R, nwaves, (T *)resid, mpx_jacobi_peer{}, (const T *)nullptr)
+                       R, nwaves, (T *)resid, mpx_jacobi_peer{}, (const T *)nullptr, (T)0)
 #define MPX_JVN(T)                                                                                             \
     hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 1>), g, b, 0, s, (const T *)u, (T *)un, cols, pitch, r0, r1,    \
-                       strips, R, nwaves, (T *)resid, mpx_jacobi_peer{}, (const T *)nullptr)
+                       strips, R, nwaves, (T *)resid, mpx_jacobi_peer{}, (const T *)nullptr, (T)0)
 #define MPX_JVA(T)                                                                                             \
     hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 0, true, false, true>), g, b, 0, s, (const T *)u, (T *)un, cols,  \
-                       pitch, r0, r1, strips, R, nwaves, (T *)resid, mpx_jacobi_peer{}, (const T *)nullptr)
+                       pitch, r0, r1, strips, R, nwaves, (T *)resid, mpx_jacobi_peer{}, (const T *)nullptr, (T)0)
 #define MPX_JVW(T)                                                                                             \
     hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 0, true, false, true, 16>), dim3((nwaves + 15) / 16), dim3(1024),  \
                        0, s, (const T *)u, (T *)un, cols, pitch, r0, r1, strips, R, nwaves, (T *)resid,               \
-                       mpx_jacobi_peer{}, (const T *)nullptr)
+                       mpx_jacobi_peer{}, (const T *)nullptr, (T)0)
 #define MPX_JVI(T)                                                                                             \
     hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 2, true, false, true>), g, b, 0, s, (const T *)u, (T *)un, cols,  \
-                       pitch, r0, r1, strips, R, nwaves, (T *)resid, mpx_jacobi_peer{}, (const T *)nullptr)
+                       pitch, r0, r1, strips, R, nwaves, (T *)resid, mpx_jacobi_peer{}, (const T *)nullptr, (T)0)
 #define MPX_JVX(T)                                                                                             \
     hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 0, false>), g, b, 0, s, (const T *)u, (T *)un, cols, pitch, r0, \
-                       r1, strips, R, nwaves, (T *)resid, mpx_jacobi_peer{}, (const T *)nullptr)
+                       r1, strips, R, nwaves, (T *)resid, mpx_jacobi_peer{}, (const T *)nullptr, (T)0)
     if (fp64) {
         if (aux == 22) MPX_JVI(double); else if (aux == 50) MPX_JVW(double); else if (aux == 18) MPX_JVA(double); else if (aux == 10) MPX_JVX(double); else if (aux == 6) MPX_JVN(double); else if (aux) MPX_JV(double, 2); else MPX_JV(double, 0);
     } else {
@@ -73,13 +73,45 @@ extern "C" int mpx_jacobi_rhs_variant(void *u, const void *b, void *un, int cols
     hipStream_t s = as_stream(stream);
 #define MPX_JR(T, NT)                                                                                            \
     hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 0, true, false, true, 4, true, NT>), g, blk, 0, s, (const T *)u, \
-                       (T *)un, cols, pitch, r0, r1, strips, R, nwaves, (T *)resid, mpx_jacobi_peer{}, (const T *)b)
+                       (T *)un, cols, pitch, r0, r1, strips, R, nwaves, (T *)resid, mpx_jacobi_peer{}, (const T *)b, (T)0)
     if (fp64) {
         if (nt) MPX_JR(double, true); else MPX_JR(double, false);
     } else {
         if (nt) MPX_JR(float, true); else MPX_JR(float, false);
     }
 #undef MPX_JR
+    MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
+    return MPX_OK;
+}
+
+// The production templates of the Chebyshev step, <T, 2, 0, true, false, true,
+// 4, RHS, RHS, ACCEL = true> (b null: the Laplace form), at an explicit rows-
+// per-wave R (row-block tests). un is in-out.
+extern "C" int mpx_jacobi_accel_variant(void *u, const void *b, void *un, int cols, int pitch, int r0, int r1,
+                                        double omega, void *resid, int fp64, int R, void *stream) {
+    using namespace mpx;
+    MPX_CHECK_ARG(u && un && cols >= 1 && pitch >= cols && r0 >= 1 && r1 >= r0 && R >= 1, "bad arguments");
+    MPX_CHECK_ARG(omega > 0.0 && omega <= (fp64 ? 1.7976931348623157e308 : 3.402823466e38) &&
+                      (fp64 || (float)omega > 0.0f),
+                  "omega must be finite and positive");
+    const int NV = fp64 ? 2 : 4;
+    MPX_CHECK_ARG(pitch % NV == 0 && cols % NV == 0 && aligned16(u) && (!b || aligned16(b)) && aligned16(un),
+                  "needs the vector layout");
+    if (r1 == r0) return MPX_OK;
+    const int strips = (cols / NV + kStripVec - 1) / kStripVec;
+    const int nwaves = strips * ((r1 - r0 + R - 1) / R);
+    const dim3 g((nwaves + 3) / 4), blk(256);
+    hipStream_t s = as_stream(stream);
+#define MPX_JA(T, RHS)                                                                                          \
+    hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 0, true, false, true, 4, RHS, RHS && kRhsNT, true>), g, blk, 0, s, \
+                       (const T *)u, (T *)un, cols, pitch, r0, r1, strips, R, nwaves, (T *)resid, mpx_jacobi_peer{},  \
+                       (const T *)b, (T)omega)
+    if (fp64) {
+        if (b) MPX_JA(double, true); else MPX_JA(double, false);
+    } else {
+        if (b) MPX_JA(float, true); else MPX_JA(float, false);
+    }
+#undef MPX_JA
     MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
     return MPX_OK;
 }

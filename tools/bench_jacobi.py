@@ -20,6 +20,11 @@ VERDICT r2 #3); a mismatch exits 3.
 --rhs: the Poisson sweep (-Laplace(u) = f) with a seeded source term b in
 [-2^-10, 2^-10) — three words per point instead of two — through the same
 transports, with the same N-rank == one-device verification.
+
+--accel: Chebyshev acceleration (SlabJacobi(accel="chebyshev")): one more word
+per point, the iterate before last; composable with --rhs, --fp32 and --halo,
+verified the same way. The steps run eagerly also with --graph (omega changes
+every iteration).
 """
 import argparse
 import json
@@ -50,6 +55,7 @@ def main() -> int:
     p.add_argument("--graph", action="store_true", help="replay HIP graphs of whole residual cycles")
     p.add_argument("--progress", action="store_true", help="per-phase and per-check timing on stderr")
     p.add_argument("--rhs", action="store_true", help="Poisson sweep with a seeded right-hand side (off: Laplace)")
+    p.add_argument("--accel", action="store_true", help="Chebyshev acceleration (off: plain Jacobi)")
     p.add_argument("--no-verify", action="store_true", help="skip the N-rank == one-device comparison")
     p.add_argument("--gpus", type=int, default=None,
                    help="ranks to run (self-launched when no torchrun environment); default WORLD_SIZE or 1")
@@ -66,7 +72,8 @@ def main() -> int:
     dt = torch.float32 if a.fp32 else torch.float64
     rows = a.rows or a.size
     sol = SlabJacobi(ctx, rows, a.size, dtype=dt, check_every=a.check_every,
-                     overlap={"auto": "auto", "on": True, "off": False}[a.overlap], halo=a.halo)
+                     overlap={"auto": "auto", "on": True, "off": False}[a.overlap], halo=a.halo,
+                     accel="chebyshev" if a.accel else None)
     def say(msg):
         if a.progress:
             print(f"[jacobi r{ctx.rank} {time.perf_counter() - t_start:8.3f}s] {msg}", file=sys.stderr, flush=True)
@@ -114,13 +121,14 @@ def main() -> int:
             "dtype": "fp32" if a.fp32 else "fp64", "check_every": a.check_every,
             "gpoints_per_s": round(rows * a.size / (ms * 1e-3) / 1e9, 3),
             "rhs": bool(a.rhs),
-            "TBps_aggregate": round((3 if a.rhs else 2) * rows * a.size * es / (ms * 1e-3) / 1e12, 3),
+            "accel": "chebyshev" if a.accel else None,
+            "TBps_aggregate": round((2 + bool(a.rhs) + bool(a.accel)) * rows * a.size * es / (ms * 1e-3) / 1e12, 3),
             "residual": sol.last_residual,
             "transport": sol.transport,
             "halo": ("one-launch" if sol.peer is not None else "overlap" if sol.overlap else "inorder")
             if ctx.world > 1 else None,
             **span.fields(a.iters),
-            "hip_graph": bool(a.graph and ctx.device.type == "cuda"),
+            "hip_graph": bool(a.graph and ctx.device.type == "cuda" and not a.accel),
             "peer_probe": ("ok" if sol.peer is not None else "fallback")
             if ctx.world > 1 and a.halo in ("auto", "peer") and ctx.device.type == "cuda" else None,
             "verified": verified,
@@ -143,7 +151,8 @@ def one_device_equal(got, sol, rows, a, dt, ctx) -> bool:
     device alone, compare with the gathered N-rank field."""
     from cuda_mpi_openmp_amd.parallel.slab import Slab
 
-    ref = SlabJacobi(parallel.DistContext(device=ctx.device), rows, a.size, dtype=dt, check_every=a.check_every)
+    ref = SlabJacobi(parallel.DistContext(device=ctx.device), rows, a.size, dtype=dt, check_every=a.check_every,
+                     accel="chebyshev" if a.accel else None)
     ref.set_boundary(top=1.0)
     parts = []
     for r in range(ctx.world):
