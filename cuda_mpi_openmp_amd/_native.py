@@ -100,6 +100,14 @@ _SIGNATURES = {
     "mpx_jacobi_peer_sweep_accel": (c_int, [c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, ctypes.c_double, c_vp,
                                             c_vp, c_vp]),
     "mpx_cpu_jacobi_accel_f64": (ctypes.c_double, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.c_double]),
+    # 3-D sweeps: (u, b or NULL, un, nx, ny, k0, k1, [omega,] resid, stream)
+    "mpx_jacobi3d_f64": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "mpx_jacobi3d_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "mpx_jacobi3d_accel_f64": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.c_double, c_vp, c_vp]),
+    "mpx_jacobi3d_accel_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.c_double, c_vp, c_vp]),
+    "mpx_jacobi3d_tile": (c_int, [c_int, c_int, c_int, _ip]),
+    "mpx_cpu_jacobi3d_f64": (ctypes.c_double, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int]),
+    "mpx_cpu_jacobi3d_accel_f64": (ctypes.c_double, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.c_double]),
     "mpx_cpu_threads": (c_int, []),
     "mpx_cpu_vsub_f64": (None, [c_vp, c_vp, c_vp, c_i64]),
     "mpx_cpu_vsub_f32": (None, [c_vp, c_vp, c_vp, c_i64]),
@@ -152,6 +160,9 @@ _TUNE_SIGNATURES = {
     # (u, b or NULL, un in-out, cols, pitch, r0, r1, omega, resid, fp64, R, stream)
     "mpx_jacobi_accel_variant": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.c_double, c_vp, c_int,
                                          c_int, c_vp]),
+    # (fp64, u, b or NULL, un, nx, ny, k0, k1, accel, omega, resid, form, ty, kz, stream)
+    "mpx_jacobi3d_variant": (c_int, [c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, ctypes.c_double,
+                                     c_vp, c_int, c_int, c_int, c_vp]),
 }
 _tune = None
 

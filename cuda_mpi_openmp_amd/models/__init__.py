@@ -5,12 +5,14 @@ form and a row/shard-decomposed multi-GPU form:
   lab2  EdgeDetector / SlabEdgeDetector        Roberts cross + KxK convolutions
   lab3  PixelClassifier / SlabPixelClassifier  Mahalanobis ML classification
   stencil  SlabJacobi                          2-D Jacobi with halo exchange
+  stencil  SlabJacobi3D                        3-D Jacobi on plane slabs
 """
 
 from .classifier import PixelClassifier, SlabPixelClassifier
 from .edge import EdgeDetector, SlabEdgeDetector
 from .jacobi import SlabJacobi
+from .jacobi3d import SlabJacobi3D
 from .vector import ShardedVectorSub, VectorSub
 
-__all__ = ["PixelClassifier", "SlabPixelClassifier", "EdgeDetector", "SlabEdgeDetector", "SlabJacobi",
+__all__ = ["PixelClassifier", "SlabPixelClassifier", "EdgeDetector", "SlabEdgeDetector", "SlabJacobi", "SlabJacobi3D",
            "ShardedVectorSub", "VectorSub"]

@@ -6,7 +6,7 @@ from .classify import plan as classify_plan
 from .edge import ConvLauncher, conv, conv_rows, roberts, roberts_rgb
 from .filters import Filter, get_filter, list_filters
 from .sort import argsort, sort, sort_, sort_pairs_
-from .stencil import jacobi_sweep
+from .stencil import jacobi3d_sweep, jacobi3d_tile, jacobi_sweep
 from .vector import vsub
 
 __all__ = [
@@ -22,6 +22,8 @@ __all__ = [
     "get_filter",
     "list_filters",
     "jacobi_sweep",
+    "jacobi3d_sweep",
+    "jacobi3d_tile",
     "argsort",
     "sort",
     "sort_",

@@ -140,3 +140,38 @@ def jacobi(u: torch.Tensor, r0: int, r1: int, keep_dtype: bool = False,
     un[r0:r1, 1:-1] = s
     del c
     return un
+
+
+def jacobi3d(u: torch.Tensor, k0: int, k1: int, keep_dtype: bool = False,
+             rhs: torch.Tensor | None = None, omega: float | None = None,
+             prev: torch.Tensor | None = None) -> torch.Tensor:
+    """One 3-D sweep over planes [k0, k1) of a (planes + 2, ny, nx) slab (halo
+    planes at 0 and planes + 1), in fp64, or with ``keep_dtype`` in u's own
+    dtype, in the kernels' association:
+    s = ((((zm + zp) + (ym + yp)) + (xm + xp)) [+ rhs]) * c with c = 1/6 rounded
+    once to the working dtype and every operation rounded, so the native result
+    must equal it bit for bit. ``omega`` with ``prev`` (u's shape: the iterate
+    before u): prev + omega * (s - prev) at the interior points of the swept
+    planes. Every other element of the result is u's."""
+    u = u.cpu() if keep_dtype else u.cpu().to(torch.float64)
+    if u.dim() != 3:
+        raise ValueError("u must be a (planes + 2, ny, nx) tensor")
+    un = u.clone()
+    z, y, x = slice(k0, k1), slice(1, -1), slice(1, -1)
+    s = ((u[k0 - 1:k1 - 1, y, x] + u[k0 + 1:k1 + 1, y, x]) + (u[z, :-2, x] + u[z, 2:, x])) + (u[z, y, :-2] + u[z, y, 2:])
+    if rhs is not None:
+        b = rhs.cpu().to(u.dtype)
+        if b.shape != u.shape:
+            raise ValueError("rhs must have u's shape")
+        s = s + b[z, y, x]
+    s = s * torch.tensor(1.0 / 6.0, dtype=u.dtype)
+    if (omega is None) != (prev is None):
+        raise ValueError("omega and prev come together")
+    if omega is not None:
+        p = prev.cpu().to(u.dtype)
+        if p.shape != u.shape:
+            raise ValueError("prev must have u's shape")
+        p = p[z, y, x]
+        s = p + torch.tensor(omega, dtype=u.dtype) * (s - p)
+    un[z, y, x] = s
+    return un

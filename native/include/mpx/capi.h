@@ -340,6 +340,38 @@ int mpx_jacobi_accel_f32(const float *u, const float *b, float *un, int cols, in
 int mpx_jacobi_peer_sweep_accel(int fp64, void *u, const void *b, void *un, int cols, int pitch, int rows,
                                 double omega, void *resid, const mpx_jacobi_peer *p, void *stream);
 
+/* 3-D sweeps (the 7-point Laplace / Poisson stencil). u, un and the optional b
+ * are contiguous (planes + 2) x ny x nx buffers, x fastest; planes 0 and
+ * planes + 1 are halo planes, rows 0 / ny - 1 and columns 0 / nx - 1 are
+ * Dirichlet. A sweep covers planes [k0, k1), 1 <= k0 <= k1 (empty: no-op):
+ *     s = ((((zm + zp) + (ym + yp)) + (xm + xp)) [+ b]) * c,  c = (T)(1.0 / 6.0)
+ * at the interior points, every operation rounded, never fused; boundary
+ * elements of a swept plane receive u's value, other planes are not written.
+ * b == NULL is the Laplace form. The accel entries write p + omega * (s - p)
+ * with p = un's value on entry (three rounded operations, omega rounded once
+ * to T and finite and positive before and after). resid (may be NULL): a
+ * one-element device word zeroed by the caller that receives max|s - u| over
+ * the swept interior points. Needs nx >= 3, ny >= 3, ny * nx < 2^31; plane
+ * offsets are 64-bit. Widths that are a multiple of the 16-byte vector with
+ * 16-byte aligned pointers take the wave-strip kernel, everything else the
+ * per-lane kernel (native/src/kernels/jacobi3d.hip). */
+int mpx_jacobi3d_f64(const double *u, const double *b, double *un, int nx, int ny, int k0, int k1, double *resid,
+                     void *stream);
+int mpx_jacobi3d_f32(const float *u, const float *b, float *un, int nx, int ny, int k0, int k1, float *resid,
+                     void *stream);
+int mpx_jacobi3d_accel_f64(const double *u, const double *b, double *un, int nx, int ny, int k0, int k1, double omega,
+                           double *resid, void *stream);
+int mpx_jacobi3d_accel_f32(const float *u, const float *b, float *un, int nx, int ny, int k0, int k1, double omega,
+                           float *resid, void *stream);
+/* The wave-strip form and tile of the production launches for a dtype (fp64 != 0:
+ * double) and sweep kind (rhs: with b; accel: the Chebyshev entries): out[0] =
+ * form (0: rows-in-plane walk, 1: z-march; + 2: workgroups remapped so that
+ * launch-order neighbours share an XCD), out[1] = TY (rows per wave), out[2] =
+ * KZ (planes marched per wave), out[3] = the wave count below which a launch
+ * halves its tile (rows: TY, march: KZ) until it has that many waves or the
+ * tile is 1. out: 4 ints. */
+int mpx_jacobi3d_tile(int fp64, int rhs, int accel, int *out);
+
 /* ---------------- lab5: ascending sort (no reference program) ---------------- */
 /* In place on the device; dtype is an mpx_sort_dtype. int32/float32: LSD radix sort
  * (onesweep, 8-bit digits) on order-preserving uint32 keys, bitonic network for
@@ -395,6 +427,12 @@ double mpx_cpu_jacobi_rhs_f64(const double *u, const double *b, double *un, int 
  * NaN, with nothing written, on a null u / un, bad geometry or a bad omega */
 double mpx_cpu_jacobi_accel_f64(const double *u, const double *b, double *un, int cols, int pitch, int r0, int r1,
                                 double omega);
+/* the 3-D sweeps of mpx_jacobi3d_f64 / mpx_jacobi3d_accel_f64 (b may be NULL);
+ * both return the residual, or NaN, with nothing written, on a null u / un,
+ * bad geometry or a bad omega */
+double mpx_cpu_jacobi3d_f64(const double *u, const double *b, double *un, int nx, int ny, int k0, int k1);
+double mpx_cpu_jacobi3d_accel_f64(const double *u, const double *b, double *un, int nx, int ny, int k0, int k1,
+                                  double omega);
 void mpx_cpu_sort(void *data, int64_t n, int dtype);
 void mpx_cpu_sort_pairs(void *keys, uint32_t *vals, int64_t n, int dtype, int flags);
 

@@ -456,6 +456,64 @@ double mpx_cpu_jacobi_accel_f64(const double *u, const double *b, double *un, in
     return res;
 }
 
+/* 3-D sweep over planes [k0, k1) of a (planes + 2, ny, nx) buffer, x fastest:
+ * s = ((((zm + zp) + (ym + yp)) + (xm + xp)) [+ b]) * (1/6), every operation
+ * rounded (-ffp-contract=off), in the GPU kernels' association. Boundary rows
+ * and columns of a swept plane are copied through. omega == NULL: un = s;
+ * otherwise the Chebyshev step un = un + omega * (s - un), un in-out. */
+static double jacobi3d_planes(const double *u, const double *b, double *un, int nx, int ny, int k0, int k1,
+                              const double *omega) {
+    const int64_t plane = (int64_t)ny * nx;
+    const double c = 1.0 / 6.0;
+    double res = 0.0;
+    int k;
+#pragma omp parallel for schedule(static) reduction(max : res)
+    for (k = k0; k < k1; ++k) {
+        const double *uc = u + (int64_t)k * plane;
+        const double *bc = b ? b + (int64_t)k * plane : NULL;
+        double *o = un + (int64_t)k * plane;
+        for (int y = 0; y < ny; ++y) {
+            const int64_t r = (int64_t)y * nx;
+            if (y == 0 || y == ny - 1) {
+                for (int x = 0; x < nx; ++x) o[r + x] = uc[r + x];
+                continue;
+            }
+            o[r] = uc[r];
+            o[r + nx - 1] = uc[r + nx - 1];
+            for (int x = 1; x < nx - 1; ++x) {
+                const int64_t i = r + x;
+                const double n6 = ((uc[i - plane] + uc[i + plane]) + (uc[i - nx] + uc[i + nx])) + (uc[i - 1] + uc[i + 1]);
+                const double s = bc ? (n6 + bc[i]) * c : n6 * c;
+                const double d = fabs(s - uc[i]);
+                res = d > res ? d : res;
+                if (omega) {
+                    const double p = o[i];
+                    const double t = *omega * (s - p);
+                    o[i] = p + t;
+                } else {
+                    o[i] = s;
+                }
+            }
+        }
+    }
+    return res;
+}
+
+static int jacobi3d_geometry_ok(const void *u, const void *un, int nx, int ny, int k0, int k1) {
+    return u && un && nx >= 3 && ny >= 3 && (int64_t)ny * nx < ((int64_t)1 << 31) && k0 >= 1 && k1 >= k0;
+}
+
+double mpx_cpu_jacobi3d_f64(const double *u, const double *b, double *un, int nx, int ny, int k0, int k1) {
+    if (!jacobi3d_geometry_ok(u, un, nx, ny, k0, k1)) return NAN;
+    return jacobi3d_planes(u, b, un, nx, ny, k0, k1, NULL);
+}
+
+double mpx_cpu_jacobi3d_accel_f64(const double *u, const double *b, double *un, int nx, int ny, int k0, int k1,
+                                  double omega) {
+    if (!jacobi3d_geometry_ok(u, un, nx, ny, k0, k1) || !(omega > 0.0) || !isfinite(omega)) return NAN;
+    return jacobi3d_planes(u, b, un, nx, ny, k0, k1, &omega);
+}
+
 /* Host statistics with the reference's exact operation order
  * (reference lab3/src/main.cu:102-152): mean, unbiased covariance, cofactor
  * determinant and the modular-index adjugate inverse. */

@@ -30,6 +30,9 @@ double mpx_cpu_jacobi_f64(const double *u, double *un, int cols, int pitch, int 
 double mpx_cpu_jacobi_rhs_f64(const double *u, const double *b, double *un, int cols, int pitch, int r0, int r1);
 double mpx_cpu_jacobi_accel_f64(const double *u, const double *b, double *un, int cols, int pitch, int r0, int r1,
                                 double omega);
+double mpx_cpu_jacobi3d_f64(const double *u, const double *b, double *un, int nx, int ny, int k0, int k1);
+double mpx_cpu_jacobi3d_accel_f64(const double *u, const double *b, double *un, int nx, int ny, int k0, int k1,
+                                  double omega);
 /* lab5: ascending sort in place, same order as mpx_sort (dtype: enum mpx_sort_dtype). */
 void mpx_cpu_sort(void *data, int64_t n, int dtype);
 /* Stable key-value sort, same order and flags as mpx_sort_pairs_ws (capi.h:

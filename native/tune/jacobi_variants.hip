@@ -2,8 +2,10 @@
 // explicit rows per wave R and the A/B forms of round 2-3 (buffer-store cache
 // policy, non-temporal loads, no tail exit, alternating walks, 16-wave
 // workgroups). Built into libmpx_tune.so only; production launches are in
-// native/src/kernels/jacobi.hip.
+// native/src/kernels/jacobi.hip. The 3-D entry (explicit wave form and tile of
+// the kernels in jacobi3d.hpp, production launches in jacobi3d.hip) is at the end.
 #include "../src/kernels/jacobi_wave.hpp"
+#include "../src/kernels/jacobi3d.hpp"
 
 // Tuning entry point (tools/jbench.py): wave kernel with an explicit rows-per-
 // wave R and buffer-store cache policy aux (0 default, 2 = nontemporal).
@@ -114,4 +116,56 @@ extern "C" int mpx_jacobi_accel_variant(void *u, const void *b, void *un, int co
 #undef MPX_JA
     MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
     return MPX_OK;
+}
+
+// 3-D sweeps (native/src/kernels/jacobi3d.hpp) with an explicit wave form and
+// tile, so tests run production tile shapes at tiny sizes and the bench tool
+// measures both forms: form 0 = rows (ty rows per wave, kz must be 1), form 1 =
+// march (ty in {2, 4, 8} rows x kz planes per wave), forms 2 and 3 = the same
+// with the workgroups remapped per XCD. b null: the Laplace form; accel != 0:
+// the Chebyshev step with omega, un in-out.
+extern "C" int mpx_jacobi3d_variant(int fp64, const void *u, const void *b, void *un, int nx, int ny, int k0, int k1,
+                                    int accel, double omega, void *resid, int form, int ty, int kz, void *stream) {
+    using namespace mpx;
+    MPX_CHECK_ARG(form >= 0 && form <= 3, "form must be 0 (rows), 1 (march), 2 or 3 (the same, XCD-remapped)");
+    MPX_CHECK_ARG((form & 1) == 0 ? (ty >= 1 && kz == 1) : ((ty == 2 || ty == 4 || ty == 8) && kz >= 1),
+                  "tile: rows takes ty >= 1 and kz == 1, march ty in {2, 4, 8} and kz >= 1");
+    hipStream_t s = as_stream(stream);
+#define MPX_J3A(T, RHS, ACCEL, REMAP)                                                                                \
+    do {                                                                                                             \
+        if ((form & 1) == 0)                                                                                         \
+            return launch_j3_rows<T, RHS, ACCEL, REMAP>((const T *)u, (const T *)b, (T *)un, nx, ny, k0, k1, ty, w,  \
+                                                        (T *)resid, s);                                              \
+        if (ty == 2)                                                                                                 \
+            return launch_j3_march<T, 2, RHS, ACCEL, REMAP>((const T *)u, (const T *)b, (T *)un, nx, ny, k0, k1, kz, \
+                                                            w, (T *)resid, s);                                       \
+        if (ty == 4)                                                                                                 \
+            return launch_j3_march<T, 4, RHS, ACCEL, REMAP>((const T *)u, (const T *)b, (T *)un, nx, ny, k0, k1, kz, \
+                                                            w, (T *)resid, s);                                       \
+        return launch_j3_march<T, 8, RHS, ACCEL, REMAP>((const T *)u, (const T *)b, (T *)un, nx, ny, k0, k1, kz, w,  \
+                                                        (T *)resid, s);                                              \
+    } while (0)
+#define MPX_J3(T, RHS, ACCEL)                                                                                        \
+    do {                                                                                                             \
+        T w;                                                                                                         \
+        if (const int rc = j3_check<T>(u, un, nx, ny, k0, k1, ACCEL, omega, &w)) return rc;                          \
+        MPX_CHECK_ARG(j3_vector_layout((const T *)u, (const T *)b, (const T *)un, nx), "needs the vector layout");   \
+        if (k1 == k0) return MPX_OK;                                                                                 \
+        if (form & 2) MPX_J3A(T, RHS, ACCEL, true);                                                                  \
+        MPX_J3A(T, RHS, ACCEL, false);                                                                               \
+    } while (0)
+#define MPX_J3K(T)                                                                                                   \
+    do {                                                                                                             \
+        if (accel) {                                                                                                 \
+            if (b) MPX_J3(T, true, true);                                                                            \
+            MPX_J3(T, false, true);                                                                                  \
+        }                                                                                                            \
+        if (b) MPX_J3(T, true, false);                                                                               \
+        MPX_J3(T, false, false);                                                                                     \
+    } while (0)
+    if (fp64) MPX_J3K(double);
+    MPX_J3K(float);
+#undef MPX_J3K
+#undef MPX_J3
+#undef MPX_J3A
 }
