@@ -100,6 +100,21 @@ _SIGNATURES = {
     "mpx_jacobi_peer_sweep_accel": (c_int, [c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, ctypes.c_double, c_vp,
                                             c_vp, c_vp]),
     "mpx_cpu_jacobi_accel_f64": (ctypes.c_double, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.c_double]),
+    # damped sweeps (multigrid smoother): (u, b or NULL, un out, cols, pitch, r0, r1, omega, resid, stream)
+    "mpx_jacobi_relax_f64": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.c_double, c_vp, c_vp]),
+    "mpx_jacobi_relax_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.c_double, c_vp, c_vp]),
+    "mpx_cpu_jacobi_relax_f64": (ctypes.c_double, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.c_double]),
+    # multigrid: residual (u, b or NULL, r, rows, cols, pitch_u, pitch_b, pitch_r, resid, stream),
+    # restrict (r, bc, hc, wc, pitch_r, pitch_bc, stream), prolong_add (e, u, hc, wc, pitch_e, pitch_u, stream)
+    "mpx_mg_residual_f64": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "mpx_mg_residual_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "mpx_mg_restrict_f64": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
+    "mpx_mg_restrict_f32": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
+    "mpx_mg_prolong_add_f64": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
+    "mpx_mg_prolong_add_f32": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
+    "mpx_cpu_mg_residual_f64": (ctypes.c_double, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int]),
+    "mpx_cpu_mg_restrict_f64": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int]),
+    "mpx_cpu_mg_prolong_add_f64": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int]),
     # 3-D sweeps: (u, b or NULL, un, nx, ny, k0, k1, [omega,] resid, stream)
     "mpx_jacobi3d_f64": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "mpx_jacobi3d_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),

@@ -6,13 +6,15 @@ form and a row/shard-decomposed multi-GPU form:
   lab3  PixelClassifier / SlabPixelClassifier  Mahalanobis ML classification
   stencil  SlabJacobi                          2-D Jacobi with halo exchange
   stencil  SlabJacobi3D                        3-D Jacobi on plane slabs
+  stencil  PoissonMultigrid                    2-D Poisson by geometric multigrid V-cycles (one device)
 """
 
 from .classifier import PixelClassifier, SlabPixelClassifier
 from .edge import EdgeDetector, SlabEdgeDetector
 from .jacobi import SlabJacobi
 from .jacobi3d import SlabJacobi3D
+from .multigrid import PoissonMultigrid
 from .vector import ShardedVectorSub, VectorSub
 
 __all__ = ["PixelClassifier", "SlabPixelClassifier", "EdgeDetector", "SlabEdgeDetector", "SlabJacobi", "SlabJacobi3D",
-           "ShardedVectorSub", "VectorSub"]
+           "PoissonMultigrid", "ShardedVectorSub", "VectorSub"]

@@ -1,0 +1,199 @@
+"""Geometric multigrid V-cycle for the 2-D Poisson problem -Laplace(u) = f on one
+device, in ``SlabJacobi``'s layout and discretisation (b = h^2 f, Dirichlet
+values in the first / last buffer row and column; the fixed point satisfies
+4 u - (sum of the neighbours) = b).
+
+Level 0 is the (rows + 2, cols) grid. A level (H, W) has the coarse level
+(Hc, Wc) with H = 2 Hc - 1, W = 2 Wc - 1 while H - 1 and W - 1 are both even
+and the coarse grid keeps an interior. One V(nu1, nu2) cycle at level l:
+
+  1. nu1 damped Jacobi sweeps (``ops.jacobi_relax``);
+  2. the residual r = b + sum(neighbours) - 4 u (``ops.mg_residual``);
+  3. full weighting of r into level l+1's right-hand side (``ops.mg_restrict``);
+  4. level l+1's u <- 0 (the error equation has zero Dirichlet values);
+  5. the cycle on level l+1;
+  6. bilinear interpolation of level l+1's u added to u (``ops.mg_prolong_add_``);
+  7. nu2 damped Jacobi sweeps.
+
+The coarsest level runs ``coarse_sweeps`` sweeps, or, with a single interior
+point, one undamped sweep (the exact solve up to rounding). Every operator has
+one defined rounding order, so a GPU fp64 cycle is bit-identical to the CPU
+cycle. All buffers are allocated in the constructor, with the row pitch rounded
+up to 16 bytes so the odd widths take the vector kernels; ``cycle()``
+allocates nothing.
+"""
+
+from __future__ import annotations
+
+import math
+from typing import Callable, List, Optional, Tuple
+
+import torch
+
+from .. import ops
+
+
+class _Level:
+    """Buffers of one grid level: pitched (H, W) views u, un, b, r."""
+
+    def __init__(self, h: int, w: int, dtype, device, with_r: bool):
+        nv = 16 // torch.empty((), dtype=dtype).element_size()
+        pitch = (w + nv - 1) // nv * nv
+        self.h, self.w = h, w
+        self._bufs = []
+
+        def grid() -> torch.Tensor:
+            buf = torch.zeros((h, pitch), dtype=dtype, device=device)
+            self._bufs.append(buf)
+            return buf[:, :w]
+
+        self.u, self.un, self.b = grid(), grid(), grid()
+        self.r = grid() if with_r else None
+
+    def zero_u(self) -> None:
+        """u <- 0 on the whole backing buffer (one contiguous fill)."""
+        self.u._base.zero_()
+
+
+class PoissonMultigrid:
+    """V-cycle solver for 4 u - (sum of the neighbours) = b on a
+    (rows + 2, cols) grid with Dirichlet boundary values.
+
+    ``levels``: the list of level shapes, finest first. ``cycle()`` runs one
+    V-cycle and returns the fused max|s - u| of level 0's last post-smoothing
+    sweep (``last_residual``, ``SlabJacobi.last_residual``'s meaning);
+    ``solve(tol)`` cycles until it is at most ``tol``. ``cycles`` counts the
+    cycles run. float64 on CPU tensors, float64 / float32 on the GPU."""
+
+    def __init__(self, rows: int, cols: int, dtype=torch.float64, device=None, nu1: int = 2, nu2: int = 2,
+                 omega: float = 0.8, coarse_sweeps: int = 50, max_levels: Optional[int] = None):
+        if rows < 1 or cols < 3:
+            raise ValueError("need at least 1 interior row and 3 columns")
+        if nu1 < 0 or nu2 < 1:
+            raise ValueError("need nu1 >= 0 and nu2 >= 1 (the residual comes from the last post-smoothing sweep)")
+        if coarse_sweeps < 1:
+            raise ValueError("need coarse_sweeps >= 1")
+        omega = float(omega)
+        if not (math.isfinite(omega) and omega > 0.0):
+            raise ValueError("omega must be finite and positive")
+        if max_levels is not None and max_levels < 1:
+            raise ValueError("max_levels must be at least 1")
+        self.device = torch.device("cpu" if device is None else device)
+        if self.device.type != "cuda" and dtype != torch.float64:
+            raise ValueError("the CPU model is float64")
+        if dtype not in (torch.float64, torch.float32):
+            raise ValueError("PoissonMultigrid supports float64/float32")
+        self.rows, self.cols, self.dtype = rows, cols, dtype
+        self.nu1, self.nu2, self.omega, self.coarse_sweeps = int(nu1), int(nu2), omega, int(coarse_sweeps)
+        self.levels: List[Tuple[int, int]] = self.level_shapes(rows, cols, max_levels)
+        # a level's r feeds the restriction, so the coarsest level has none
+        self._lv = [_Level(h, w, dtype, self.device, with_r=k + 1 < len(self.levels))
+                    for k, (h, w) in enumerate(self.levels)]
+        self.resid = torch.zeros(1, dtype=dtype, device=self.device)
+        self.cycles = 0
+        self.last_residual: Optional[float] = None
+
+    @staticmethod
+    def level_shapes(rows: int, cols: int, max_levels: Optional[int] = None) -> List[Tuple[int, int]]:
+        shapes = [(rows + 2, cols)]
+        while max_levels is None or len(shapes) < max_levels:
+            h, w = shapes[-1]
+            if (h - 1) % 2 or (w - 1) % 2:
+                break
+            hc, wc = (h + 1) // 2, (w + 1) // 2
+            if hc < 3 or wc < 3:
+                break
+            shapes.append((hc, wc))
+        return shapes
+
+    # ------------------------------------------------------------------ setup
+    @property
+    def u(self) -> torch.Tensor:
+        """Level 0's current iterate, an (H, W) view."""
+        return self._lv[0].u
+
+    @property
+    def rhs(self) -> torch.Tensor:
+        return self._lv[0].b
+
+    def set_boundary(self, top: float = 1.0, bottom: float = 0.0, left: float = 0.0, right: float = 0.0) -> None:
+        f = self._lv[0]
+        for t in (f.u, f.un):
+            t[:, 0] = left
+            t[:, -1] = right
+            t[0, :] = top
+            t[-1, :] = bottom
+
+    def fill(self, fn: Optional[Callable[[torch.Tensor, torch.Tensor], torch.Tensor]] = None, seed: int = 0) -> None:
+        """Interior initial values: fn(row_index, col_index) or seeded noise
+        (``SlabJacobi.fill``'s values at world size 1)."""
+        f = self._lv[0]
+        if fn is None:
+            g = torch.Generator(device="cpu").manual_seed(seed)
+            vals = torch.rand((self.rows, self.cols - 2), generator=g, dtype=torch.float64).to(self.device)
+        else:
+            rows = torch.arange(0, self.rows, device=self.device).unsqueeze(1)
+            cols = torch.arange(1, self.cols - 1, device=self.device).unsqueeze(0)
+            vals = fn(rows, cols)
+        f.u[1:-1, 1:-1] = torch.as_tensor(vals, device=self.device).to(self.dtype)
+        f.un.copy_(f.u)
+
+    def set_rhs(self, fn: Optional[Callable[[torch.Tensor, torch.Tensor], torch.Tensor]] = None,
+                tensor: Optional[torch.Tensor] = None) -> None:
+        """Right-hand side b = h^2 f: ``fn(row_index, col_index)`` over the
+        interior, or ``tensor``, the owned rows as (rows, cols)."""
+        if (fn is None) == (tensor is None):
+            raise ValueError("set_rhs takes exactly one of fn and tensor")
+        b = self._lv[0].b
+        if tensor is not None:
+            if tuple(tensor.shape) != (self.rows, self.cols):
+                raise ValueError(f"rhs tensor must hold the owned rows, shape {(self.rows, self.cols)}")
+            b[1:-1] = tensor.to(self.device, self.dtype)
+        else:
+            rows = torch.arange(0, self.rows, device=self.device).unsqueeze(1)
+            cols = torch.arange(1, self.cols - 1, device=self.device).unsqueeze(0)
+            b[1:-1, 1:-1] = torch.as_tensor(fn(rows, cols), device=self.device).to(self.dtype)
+
+    # ------------------------------------------------------------------ cycle
+    def _relax(self, lv: _Level, omega: float, track: bool = False) -> None:
+        ops.jacobi_relax(lv.u, lv.un, 1, lv.h - 1, omega, self.resid if track else None, rhs=lv.b)
+        lv.u, lv.un = lv.un, lv.u
+
+    def _vcycle(self, k: int) -> None:
+        lv = self._lv[k]
+        if k + 1 == len(self._lv) and k > 0:
+            if lv.h == 3 and lv.w == 3:
+                self._relax(lv, 1.0)
+            else:
+                for _ in range(self.coarse_sweeps):
+                    self._relax(lv, self.omega)
+            return
+        for _ in range(self.nu1):
+            self._relax(lv, self.omega)
+        if k + 1 < len(self._lv):
+            nx = self._lv[k + 1]
+            ops.mg_residual(lv.u, lv.r, rhs=lv.b)
+            ops.mg_restrict(lv.r, nx.b)
+            nx.zero_u()
+            self._vcycle(k + 1)
+            ops.mg_prolong_add_(nx.u, lv.u)
+        for s in range(self.nu2):
+            self._relax(lv, self.omega, track=(k == 0 and s == self.nu2 - 1))
+
+    def cycle(self) -> float:
+        """One V-cycle; one host read (the residual)."""
+        self.resid.zero_()
+        self._vcycle(0)
+        self.cycles += 1
+        self.last_residual = float(self.resid.item())
+        return self.last_residual
+
+    def solve(self, tol: float, max_cycles: int = 50) -> int:
+        """Cycle until ``last_residual <= tol`` or ``max_cycles`` cycles have
+        run; returns the number of cycles run by this call."""
+        n = 0
+        while n < max_cycles:
+            n += 1
+            if self.cycle() <= tol:
+                break
+        return n

@@ -5,6 +5,7 @@ from .classify import class_stats, classify_
 from .classify import plan as classify_plan
 from .edge import ConvLauncher, conv, conv_rows, roberts, roberts_rgb
 from .filters import Filter, get_filter, list_filters
+from .multigrid import jacobi_relax, mg_prolong_add_, mg_residual, mg_restrict
 from .sort import argsort, sort, sort_, sort_pairs_
 from .stencil import jacobi3d_sweep, jacobi3d_tile, jacobi_sweep
 from .vector import vsub
@@ -24,6 +25,10 @@ __all__ = [
     "jacobi_sweep",
     "jacobi3d_sweep",
     "jacobi3d_tile",
+    "jacobi_relax",
+    "mg_residual",
+    "mg_restrict",
+    "mg_prolong_add_",
     "argsort",
     "sort",
     "sort_",

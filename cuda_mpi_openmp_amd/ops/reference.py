@@ -175,3 +175,63 @@ def jacobi3d(u: torch.Tensor, k0: int, k1: int, keep_dtype: bool = False,
         s = p + torch.tensor(omega, dtype=u.dtype) * (s - p)
     un[z, y, x] = s
     return un
+
+
+def mg_residual(u: torch.Tensor, rhs: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Multigrid residual in u's own dtype, in the kernels' association:
+    r = ((((up + dn) + (l + rt)) [+ b]) - 4 c) at the interior points of an
+    (H, W) grid. Every other element of the result is ``out``'s (zeros without
+    ``out``): the kernels leave r's boundary alone."""
+    u = u.cpu()
+    r = torch.zeros_like(u) if out is None else out.cpu().to(u.dtype).clone()
+    n = (u[:-2, 1:-1] + u[2:, 1:-1]) + (u[1:-1, :-2] + u[1:-1, 2:])
+    if rhs is not None:
+        b = rhs.cpu().to(u.dtype)
+        if b.shape != u.shape:
+            raise ValueError("rhs must have u's shape")
+        n = n + b[1:-1, 1:-1]
+    r[1:-1, 1:-1] = n - u[1:-1, 1:-1] * 4.0
+    return r
+
+
+def mg_restrict(r: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Full weighting of a fine (2 Hc - 1, 2 Wc - 1) residual into the coarse
+    interior, scaled for the h^2-scaled coarse right-hand side, in r's dtype:
+    bc = (r[i,j] + e*0.5) + d*0.25 with e = (n + s) + (w + e) and
+    d = (nw + ne) + (sw + se), every operation rounded. Every other element of
+    the (Hc, Wc) result is ``out``'s (zeros without ``out``)."""
+    r = r.cpu()
+    h, w = r.shape
+    if h % 2 == 0 or w % 2 == 0 or h < 3 or w < 3:
+        raise ValueError("fine grid must be (2 Hc - 1, 2 Wc - 1)")
+    hc, wc = (h + 1) // 2, (w + 1) // 2
+    bc = torch.zeros((hc, wc), dtype=r.dtype) if out is None else out.cpu().to(r.dtype).clone()
+    if bc.shape != (hc, wc):
+        raise ValueError("out must be the coarse grid")
+    if hc < 3 or wc < 3:
+        return bc
+    c, up, dn = slice(2, -2, 2), slice(1, -3, 2), slice(3, -1, 2)
+    e = (r[up, c] + r[dn, c]) + (r[c, up] + r[c, dn])
+    d = (r[up, up] + r[up, dn]) + (r[dn, up] + r[dn, dn])
+    bc[1:-1, 1:-1] = (r[c, c] + e * 0.5) + d * 0.25
+    return bc
+
+
+def mg_prolong_add(e: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+    """u plus the bilinear interpolation of the coarse e at u's interior, in u's
+    dtype and the kernels' association (the vertical pair sums come first at
+    the odd rows); u's boundary is returned unchanged."""
+    u = u.cpu()
+    e = e.cpu().to(u.dtype)
+    hc, wc = e.shape
+    if u.shape != (2 * hc - 1, 2 * wc - 1):
+        raise ValueError("u must be (2 Hc - 1, 2 Wc - 1)")
+    add = torch.zeros_like(u)
+    v = e[:-1] + e[1:]  # (Hc - 1, Wc): e[I,J] + e[I+1,J]
+    add[0::2, 0::2] = e
+    add[0::2, 1::2] = (e[:, :-1] + e[:, 1:]) * 0.5
+    add[1::2, 0::2] = v * 0.5
+    add[1::2, 1::2] = (v[:, :-1] + v[:, 1:]) * 0.25
+    out = u.clone()
+    out[1:-1, 1:-1] = u[1:-1, 1:-1] + add[1:-1, 1:-1]
+    return out

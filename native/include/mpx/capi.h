@@ -339,6 +339,52 @@ int mpx_jacobi_accel_f32(const float *u, const float *b, float *un, int cols, in
                          double omega, float *resid, void *stream);
 int mpx_jacobi_peer_sweep_accel(int fp64, void *u, const void *b, void *un, int cols, int pitch, int rows,
                                 double omega, void *resid, const mpx_jacobi_peer *p, void *stream);
+/* Damped Jacobi sweep (the multigrid smoother). With s the value of the plain
+ * sweep (b NULL) or of the Poisson sweep (b given) and c = u[i][j], the
+ * interior points of rows [r0, r1) get
+ *     un[i][j] = c + omega * (s - c)
+ * as three rounded operations, omega rounded once to the buffer type (finite
+ * and positive, before and after that rounding: otherwise MPX_ERR_ARG and
+ * nothing is written). un is output only; boundary columns copy through; the
+ * residual is max|s - c|. Path selection and alignment rules are those of the
+ * sweeps above; pitch >= cols, padding is never read or written. */
+int mpx_jacobi_relax_f64(const double *u, const double *b, double *un, int cols, int pitch, int r0, int r1,
+                         double omega, double *resid, void *stream);
+int mpx_jacobi_relax_f32(const float *u, const float *b, float *un, int cols, int pitch, int r0, int r1,
+                         double omega, float *resid, void *stream);
+
+/* Geometric multigrid on an (H, W) grid with Dirichlet values in rows 0 / H-1
+ * and columns 0 / W-1 (native/src/kernels/multigrid.hip). The coarse grid of
+ * (H, W) is (hc, wc) with H = 2 hc - 1, W = 2 wc - 1; coarse (I, J) sits on
+ * fine (2I, 2J). Every buffer has its own row pitch in elements (>= its
+ * width); padding is never read for a result and never written; row offsets
+ * are 64-bit. Every + - * is one rounded operation, never an FMA. 16-byte
+ * aligned bases with pitches that are multiples of the 16-byte vector take the
+ * vector kernels, everything else the per-element kernels.
+ *
+ * residual: r = ((((up + dn) + (l + rt)) + b) - 4 c) at the interior points
+ *   (without b: no "+ b"); r's boundary is not written; resid (nullable, zeroed
+ *   by the caller) receives max|r|. rows, cols >= 3.
+ * restrict (full weighting, scaled for the h^2-scaled coarse right-hand side):
+ *   for coarse interior (I, J), i = 2I, j = 2J,
+ *     e = (r[i-1][j] + r[i+1][j]) + (r[i][j-1] + r[i][j+1])
+ *     d = (r[i-1][j-1] + r[i-1][j+1]) + (r[i+1][j-1] + r[i+1][j+1])
+ *     bc[I][J] = (r[i][j] + e * 0.5) + d * 0.25
+ *   bc's boundary is not written; r's boundary is not read for a result.
+ * prolong_add (bilinear interpolation added to u's interior, in place):
+ *     u[2I][2J]     += e[I][J]
+ *     u[2I+1][2J]   += (e[I][J] + e[I+1][J]) * 0.5
+ *     u[2I][2J+1]   += (e[I][J] + e[I][J+1]) * 0.5
+ *     u[2I+1][2J+1] += ((e[I][J] + e[I+1][J]) + (e[I][J+1] + e[I+1][J+1])) * 0.25
+ *   e's boundary is read; u's boundary is not written. hc, wc >= 2. */
+int mpx_mg_residual_f64(const double *u, const double *b, double *r, int rows, int cols, int pitch_u, int pitch_b,
+                        int pitch_r, double *resid, void *stream);
+int mpx_mg_residual_f32(const float *u, const float *b, float *r, int rows, int cols, int pitch_u, int pitch_b,
+                        int pitch_r, float *resid, void *stream);
+int mpx_mg_restrict_f64(const double *r, double *bc, int hc, int wc, int pitch_r, int pitch_bc, void *stream);
+int mpx_mg_restrict_f32(const float *r, float *bc, int hc, int wc, int pitch_r, int pitch_bc, void *stream);
+int mpx_mg_prolong_add_f64(const double *e, double *u, int hc, int wc, int pitch_e, int pitch_u, void *stream);
+int mpx_mg_prolong_add_f32(const float *e, float *u, int hc, int wc, int pitch_e, int pitch_u, void *stream);
 
 /* 3-D sweeps (the 7-point Laplace / Poisson stencil). u, un and the optional b
  * are contiguous (planes + 2) x ny x nx buffers, x fastest; planes 0 and
@@ -427,6 +473,17 @@ double mpx_cpu_jacobi_rhs_f64(const double *u, const double *b, double *un, int 
  * NaN, with nothing written, on a null u / un, bad geometry or a bad omega */
 double mpx_cpu_jacobi_accel_f64(const double *u, const double *b, double *un, int cols, int pitch, int r0, int r1,
                                 double omega);
+/* the damped sweep of mpx_jacobi_relax_f64 (b may be NULL, un output only);
+ * NaN, with nothing written, on a null u / un, bad geometry or a bad omega */
+double mpx_cpu_jacobi_relax_f64(const double *u, const double *b, double *un, int cols, int pitch, int r0, int r1,
+                                double omega);
+/* the multigrid operators of mpx_mg_*_f64. residual returns max|r| (NaN, with
+ * nothing written, on bad arguments); restrict and prolong_add return 0, or
+ * -1, with nothing written, on bad arguments */
+double mpx_cpu_mg_residual_f64(const double *u, const double *b, double *r, int rows, int cols, int pitch_u,
+                               int pitch_b, int pitch_r);
+int mpx_cpu_mg_restrict_f64(const double *r, double *bc, int hc, int wc, int pitch_r, int pitch_bc);
+int mpx_cpu_mg_prolong_add_f64(const double *e, double *u, int hc, int wc, int pitch_e, int pitch_u);
 /* the 3-D sweeps of mpx_jacobi3d_f64 / mpx_jacobi3d_accel_f64 (b may be NULL);
  * both return the residual, or NaN, with nothing written, on a null u / un,
  * bad geometry or a bad omega */

@@ -456,6 +456,114 @@ double mpx_cpu_jacobi_accel_f64(const double *u, const double *b, double *un, in
     return res;
 }
 
+/* Damped Jacobi sweep (the multigrid smoother): un = c + omega * (s - c) with c
+ * the centre value of u and s the plain (b == NULL) or Poisson value; a
+ * subtract, a multiply and an add, each rounded. un is output only; the
+ * residual is max|s - c|. NaN, with nothing written, on a null u / un, bad
+ * geometry or an omega that is not finite and positive. */
+double mpx_cpu_jacobi_relax_f64(const double *u, const double *b, double *un, int cols, int pitch, int r0, int r1,
+                                double omega) {
+    double res = 0.0;
+    int i;
+    if (!u || !un || cols < 1 || pitch < cols || r0 < 1 || r1 < r0 || !(omega > 0.0) || !isfinite(omega)) return NAN;
+#pragma omp parallel for schedule(static) reduction(max : res)
+    for (i = r0; i < r1; ++i) {
+        const double *up = u + (int64_t)(i - 1) * pitch;
+        const double *uc = u + (int64_t)i * pitch;
+        const double *ud = u + (int64_t)(i + 1) * pitch;
+        const double *bc = b ? b + (int64_t)i * pitch : NULL;
+        double *o = un + (int64_t)i * pitch;
+        o[0] = uc[0];
+        o[cols - 1] = uc[cols - 1];
+        for (int j = 1; j < cols - 1; ++j) {
+            const double n4 = (up[j] + ud[j]) + (uc[j - 1] + uc[j + 1]);
+            const double s = bc ? (n4 + bc[j]) * 0.25 : n4 * 0.25;
+            const double c = uc[j];
+            const double d = fabs(s - c);
+            res = d > res ? d : res;
+            const double t = omega * (s - c);
+            o[j] = c + t;
+        }
+    }
+    return res;
+}
+
+/* Multigrid operators on an (H, W) grid with Dirichlet rows 0 / H-1 and columns
+ * 0 / W-1 and its coarse grid (hc, wc), H = 2 hc - 1, W = 2 wc - 1 (capi.h);
+ * every operation rounded (-ffp-contract=off), in the GPU kernels' order. */
+double mpx_cpu_mg_residual_f64(const double *u, const double *b, double *r, int rows, int cols, int pitch_u,
+                               int pitch_b, int pitch_r) {
+    double res = 0.0;
+    int i;
+    if (!u || !r || rows < 3 || cols < 3 || pitch_u < cols || pitch_r < cols || (b && pitch_b < cols)) return NAN;
+#pragma omp parallel for schedule(static) reduction(max : res)
+    for (i = 1; i < rows - 1; ++i) {
+        const double *up = u + (int64_t)(i - 1) * pitch_u;
+        const double *uc = u + (int64_t)i * pitch_u;
+        const double *ud = u + (int64_t)(i + 1) * pitch_u;
+        const double *bc = b ? b + (int64_t)i * pitch_b : NULL;
+        double *o = r + (int64_t)i * pitch_r;
+        for (int j = 1; j < cols - 1; ++j) {
+            double n = (up[j] + ud[j]) + (uc[j - 1] + uc[j + 1]);
+            if (bc) n = n + bc[j];
+            const double c4 = 4.0 * uc[j];
+            const double v = n - c4;
+            const double a = fabs(v);
+            res = a > res ? a : res;
+            o[j] = v;
+        }
+    }
+    return res;
+}
+
+int mpx_cpu_mg_restrict_f64(const double *r, double *bc, int hc, int wc, int pitch_r, int pitch_bc) {
+    int I;
+    if (!r || !bc || hc < 2 || wc < 2 || hc >= (1 << 29) || wc >= (1 << 29) || pitch_r < 2 * wc - 1 || pitch_bc < wc)
+        return -1;
+#pragma omp parallel for schedule(static)
+    for (I = 1; I < hc - 1; ++I) {
+        const double *t = r + (int64_t)(2 * I - 1) * pitch_r;
+        const double *m = r + (int64_t)(2 * I) * pitch_r;
+        const double *d = r + (int64_t)(2 * I + 1) * pitch_r;
+        double *o = bc + (int64_t)I * pitch_bc;
+        for (int J = 1; J < wc - 1; ++J) {
+            const int j = 2 * J;
+            const double e = (t[j] + d[j]) + (m[j - 1] + m[j + 1]);
+            const double x = (t[j - 1] + t[j + 1]) + (d[j - 1] + d[j + 1]);
+            const double eh = e * 0.5;
+            const double xq = x * 0.25;
+            o[J] = (m[j] + eh) + xq;
+        }
+    }
+    return 0;
+}
+
+int mpx_cpu_mg_prolong_add_f64(const double *e, double *u, int hc, int wc, int pitch_e, int pitch_u) {
+    int i;
+    if (!e || !u || hc < 2 || wc < 2 || hc >= (1 << 29) || wc >= (1 << 29) || pitch_e < wc || pitch_u < 2 * wc - 1)
+        return -1;
+    const int h = 2 * hc - 1, w = 2 * wc - 1;
+#pragma omp parallel for schedule(static)
+    for (i = 1; i < h - 1; ++i) {
+        const double *c0 = e + (int64_t)(i / 2) * pitch_e;
+        const double *c1 = c0 + pitch_e; /* read on odd rows only: i / 2 + 1 <= hc - 1 there */
+        double *o = u + (int64_t)i * pitch_u;
+        for (int j = 1; j < w - 1; ++j) {
+            const int J = j / 2;
+            double v;
+            if (!(i & 1)) {
+                v = (j & 1) ? (c0[J] + c0[J + 1]) * 0.5 : c0[J];
+            } else if (!(j & 1)) {
+                v = (c0[J] + c1[J]) * 0.5;
+            } else {
+                v = ((c0[J] + c1[J]) + (c0[J + 1] + c1[J + 1])) * 0.25;
+            }
+            o[j] = o[j] + v;
+        }
+    }
+    return 0;
+}
+
 /* 3-D sweep over planes [k0, k1) of a (planes + 2, ny, nx) buffer, x fastest:
  * s = ((((zm + zp) + (ym + yp)) + (xm + xp)) [+ b]) * (1/6), every operation
  * rounded (-ffp-contract=off), in the GPU kernels' association. Boundary rows

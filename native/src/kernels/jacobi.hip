@@ -30,7 +30,8 @@ namespace {
 // term b laid out like u; same path selection, b's alignment included
 // ACCEL: the Chebyshev step un = un + omega * (s - un) (jacobi_wave.hpp), un
 // in-out; omega arrives as a double and is rounded to T once, here
-template <typename T, bool RHS = false, bool ACCEL = false>
+// RELAX: the damped sweep un = c + omega * (s - c), un output only; omega as ACCEL
+template <typename T, bool RHS = false, bool ACCEL = false, bool RELAX = false>
 int launch_jacobi(const T *u, T *un, int cols, int pitch, int r0, int r1, T *resid, void *stream,
                   const T *b = nullptr, double omega_d = 1.0) {
     MPX_CHECK_ARG(u && un && (!RHS || b), "null pointer");
@@ -38,7 +39,7 @@ int launch_jacobi(const T *u, T *un, int cols, int pitch, int r0, int r1, T *res
     // in T's range before the conversion (NaN fails the first comparison), positive after it
     const bool w_ok = omega_d > 0.0 && omega_d <= (double)std::numeric_limits<T>::max();
     const T omega = w_ok ? (T)omega_d : (T)0;
-    MPX_CHECK_ARG(!ACCEL || omega > (T)0, "omega must be finite and positive");
+    MPX_CHECK_ARG(!(ACCEL || RELAX) || omega > (T)0, "omega must be finite and positive");
     if (r1 == r0) return MPX_OK;
     constexpr int NV = JVec<T>::n;
     const bool al16 = aligned16(u) && aligned16(un) && (!RHS || aligned16(b));
@@ -54,7 +55,7 @@ int launch_jacobi(const T *u, T *un, int cols, int pitch, int r0, int r1, T *res
         int R = kJacobiRows;
         while (R > 1 && (int64_t)strips * ((rows + R - 1) / R) < 16384) R >>= 1;
         const int nwaves = strips * ((rows + R - 1) / R);
-        hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 0, true, false, true, 4, RHS, RHS && kRhsNT, ACCEL>),
+        hipLaunchKernelGGL((jacobi_wave_kernel<T, 2, 0, true, false, true, 4, RHS, RHS && kRhsNT, ACCEL, RELAX>),
                            dim3((nwaves + 3) / 4), dim3(256), 0, as_stream(stream), u, un, cols, pitch, r0, r1, strips, R, nwaves, resid,
                            mpx_jacobi_peer{}, b, omega);
         MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
@@ -65,11 +66,11 @@ int launch_jacobi(const T *u, T *un, int cols, int pitch, int r0, int r1, T *res
     const dim3 blk(256);
     const dim3 grd((lanes + 255) / 256, (r1 - r0 + kRows - 1) / kRows);
     if (vec)
-        hipLaunchKernelGGL((jacobi_kernel<T, true, RHS, ACCEL>), grd, blk, 0, as_stream(stream), u, un, cols, pitch,
-                           r0, r1, resid, b, omega);
+        hipLaunchKernelGGL((jacobi_kernel<T, true, RHS, ACCEL, RELAX>), grd, blk, 0, as_stream(stream), u, un, cols,
+                           pitch, r0, r1, resid, b, omega);
     else
-        hipLaunchKernelGGL((jacobi_kernel<T, false, RHS, ACCEL>), grd, blk, 0, as_stream(stream), u, un, cols, pitch,
-                           r0, r1, resid, b, omega);
+        hipLaunchKernelGGL((jacobi_kernel<T, false, RHS, ACCEL, RELAX>), grd, blk, 0, as_stream(stream), u, un, cols,
+                           pitch, r0, r1, resid, b, omega);
     MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
     return MPX_OK;
 }
@@ -164,6 +165,19 @@ extern "C" int mpx_jacobi_accel_f32(const float *u, const float *b, float *un, i
                                     double omega, float *resid, void *stream) {
     if (b) return mpx::launch_jacobi<float, true, true>(u, un, cols, pitch, r0, r1, resid, stream, b, omega);
     return mpx::launch_jacobi<float, false, true>(u, un, cols, pitch, r0, r1, resid, stream, nullptr, omega);
+}
+
+// damped Jacobi sweeps (the multigrid smoother): b is nullable, un output only
+extern "C" int mpx_jacobi_relax_f64(const double *u, const double *b, double *un, int cols, int pitch, int r0, int r1,
+                                    double omega, double *resid, void *stream) {
+    if (b) return mpx::launch_jacobi<double, true, false, true>(u, un, cols, pitch, r0, r1, resid, stream, b, omega);
+    return mpx::launch_jacobi<double, false, false, true>(u, un, cols, pitch, r0, r1, resid, stream, nullptr, omega);
+}
+
+extern "C" int mpx_jacobi_relax_f32(const float *u, const float *b, float *un, int cols, int pitch, int r0, int r1,
+                                    double omega, float *resid, void *stream) {
+    if (b) return mpx::launch_jacobi<float, true, false, true>(u, un, cols, pitch, r0, r1, resid, stream, b, omega);
+    return mpx::launch_jacobi<float, false, false, true>(u, un, cols, pitch, r0, r1, resid, stream, nullptr, omega);
 }
 
 extern "C" int mpx_jacobi_peer_sweep_accel(int fp64, void *u, const void *b, void *un, int cols, int pitch, int rows,

@@ -50,10 +50,15 @@ __device__ __forceinline__ T lane_of(const typename JVec<T>::type &v, int i) {
 // safe here because a lane loads exactly the elements of un it stores, each
 // before its store. The residual stays max|s - u|. ACCEL = false never reads
 // un or omega.
-template <typename T, bool VEC, bool RHS = false, bool ACCEL = false>
+// RELAX: damped Jacobi (the multigrid smoother), c + omega * (s - c) with c the
+// centre value of u, taken from the centre row already in registers: the same
+// three rounded operations, no third load stream, un output only. Never
+// together with ACCEL.
+template <typename T, bool VEC, bool RHS = false, bool ACCEL = false, bool RELAX = false>
 __global__ __launch_bounds__(256) void jacobi_kernel(const T *__restrict__ u, T *__restrict__ un, int cols,
                                                      int pitch, int r0, int r1, T *__restrict__ resid,
                                                      const T *__restrict__ b, T omega) {
+    static_assert(!(ACCEL && RELAX), "one omega form per kernel");
     using V = typename JVec<T>::type;
     constexpr int NV = VEC ? JVec<T>::n : 1;
     const int j0 = NV * (blockIdx.x * blockDim.x + threadIdx.x);
@@ -130,6 +135,10 @@ __global__ __launch_bounds__(256) void jacobi_kernel(const T *__restrict__ u, T 
                     const T d = s - prev[k];
                     const T t = omega * d;
                     res[k] = interior ? prev[k] + t : cen[k];
+                } else if constexpr (RELAX) {
+                    const T d = s - cen[k];
+                    const T t = omega * d;
+                    res[k] = interior ? cen[k] + t : cen[k];
                 } else {
                     res[k] = interior ? s : cen[k];
                 }
@@ -302,12 +311,15 @@ __device__ __forceinline__ T wave_max_dpp(T v) {
 // p is purely local, also with PEER: the neighbours read u's edge rows or the
 // mailbox copies, never un's previous contents. ACCEL = false never reads un
 // or omega.
+// RELAX: damped Jacobi, out = c + omega * (s - c) with c = cen, the centre row
+// of the u ring: no P ring, un is output only. Never together with ACCEL.
 template <typename T, int AUX = 0, int LNT = 0, bool TAIL_EXIT = true, bool PEER = false, bool ALT = false,
-          int WPB = 4, bool RHS = false, bool BNT = false, bool ACCEL = false>
+          int WPB = 4, bool RHS = false, bool BNT = false, bool ACCEL = false, bool RELAX = false>
 __global__ __launch_bounds__(64 * WPB) void jacobi_wave_kernel(const T *__restrict__ u, T *__restrict__ un, int cols,
                                                           int pitch, int r0, int r1, int strips, int rows_per_wave,
                                                           int nwaves, T *__restrict__ resid, mpx_jacobi_peer pr,
                                                           const T *__restrict__ b, T omega) {
+    static_assert(!(ACCEL && RELAX), "one omega form per kernel");
     using V = typename JWide<T>::type;
     constexpr int NV = JVec<T>::n;
     const int lane = threadIdx.x & 63;
@@ -457,6 +469,10 @@ __global__ __launch_bounds__(64 * WPB) void jacobi_wave_kernel(const T *__restri
                         const T df = sm - pv;
                         const T t = omega * df;
                         res[e] = interior ? pv + t : cen[e];
+                    } else if constexpr (RELAX) {
+                        const T df = sm - cen[e];
+                        const T t = omega * df;
+                        res[e] = interior ? cen[e] + t : cen[e];
                     } else {
                         res[e] = interior ? sm : cen[e];
                     }

@@ -1,0 +1,173 @@
+#!/usr/bin/env python3
+"""Geometric multigrid V-cycle for the 2-D Poisson problem on one MI355X
+(models.PoissonMultigrid): the time of one V(2,2) cycle, the per-kernel times at
+level 0, the solve to a tolerance, and the Chebyshev-accelerated SlabJacobi
+solve of the same problem in the same session.
+
+  python tools/bench_multigrid.py [--rows 2047] [--cols 2049] [--fp32]
+                                  [--tol 1e-8] [--reps 20] [--no-solve]
+
+Per-kernel times: device events around single launches, median over --reps
+launches that rotate through buffer sets larger than the 256 MiB Infinity
+Cache together, so no launch finds its input cached. The rates count the words
+the algorithm needs per fine point: relax 3, residual 3, restrict 1.25,
+prolong-add 2.25. ``rhs_sweep_even`` is ops.jacobi_sweep(rhs=) on the
+(rows + 2, cols - 1) grid, whose even width takes the wave-strip kernel: the
+gap to ``relax`` is what the odd width costs. ``below_level2_share`` is the
+time of the sub-cycle from level 2 down over the whole cycle (launch-bound).
+
+Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from cuda_mpi_openmp_amd import ops, parallel  # noqa: E402
+from cuda_mpi_openmp_amd.models import PoissonMultigrid, SlabJacobi  # noqa: E402
+
+MALL_BYTES = 256 << 20
+
+
+def problem_rhs(rows: int, cols: int) -> torch.Tensor:
+    g = torch.Generator(device="cpu").manual_seed(11)
+    return (torch.rand((rows, cols), generator=g, dtype=torch.float64) * 2.0 - 1.0) * 0.01
+
+
+def setup(sol, rows, cols):
+    sol.set_boundary(top=1.0)
+    sol.fill(seed=3)
+    sol.set_rhs(tensor=problem_rhs(rows, cols))
+
+
+def median_us(launch, nsets: int, reps: int, dev) -> float:
+    """Median device time of launch(k), k rotating through the buffer sets."""
+    for k in range(nsets):  # warm every set: code objects, page tables
+        launch(k)
+    torch.cuda.synchronize(dev)
+    pairs = []
+    for i in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        launch(i % nsets)
+        e1.record()
+        pairs.append((e0, e1))
+    torch.cuda.synchronize(dev)
+    return statistics.median(a.elapsed_time(b) for a, b in pairs) * 1e3
+
+
+def kernel_times(rows, cols, dt, reps, dev):
+    h, w = rows + 2, cols
+    es = 4 if dt == torch.float32 else 8
+    shapes = PoissonMultigrid.level_shapes(rows, cols, 2)
+    nsets = max(2, -(-2 * MALL_BYTES // (h * w * es)))
+    sets = [PoissonMultigrid(rows, cols, dtype=dt, device=dev, max_levels=2) for _ in range(nsets)]
+    for s in sets:  # the times do not depend on the values
+        for lv in s._lv:
+            for t in (lv.u, lv.b, lv.r):
+                if t is not None:
+                    t.uniform_(-1.0, 1.0)
+    out, pts = {}, (h - 2) * (w - 2)
+    f = [s._lv[0] for s in sets]
+    out["relax"] = (median_us(lambda k: ops.jacobi_relax(f[k].u, f[k].un, 1, h - 1, 0.8, rhs=f[k].b), nsets, reps, dev), 3)
+    out["residual"] = (median_us(lambda k: ops.mg_residual(f[k].u, f[k].r, rhs=f[k].b), nsets, reps, dev), 3)
+    if len(shapes) == 2:
+        c = [s._lv[1] for s in sets]
+        out["restrict"] = (median_us(lambda k: ops.mg_restrict(f[k].r, c[k].b), nsets, reps, dev), 1.25)
+        out["prolong_add"] = (median_us(lambda k: ops.mg_prolong_add_(c[k].u, f[k].u), nsets, reps, dev), 2.25)
+    del sets, f
+    we = w - 1  # the even width next to it: the wave-strip kernel
+    ev = [[torch.rand((h, we), dtype=dt, device=dev) for _ in range(3)] for _ in range(nsets)]
+    out["rhs_sweep_even"] = (median_us(lambda k: ops.jacobi_sweep(ev[k][0], ev[k][1], 1, h - 1, rhs=ev[k][2]), nsets, reps,
+                                       dev), 3)
+    res = {}
+    for name, (us, words) in out.items():
+        n = (h - 2) * (we - 2) if name == "rhs_sweep_even" else pts
+        res[name] = {"us": round(us, 2), "TBps": round(words * n * es / (us * 1e-6) / 1e12, 3)}
+    return res
+
+
+def main() -> int:
+    p = argparse.ArgumentParser()
+    p.add_argument("--rows", type=int, default=2047)
+    p.add_argument("--cols", type=int, default=2049)
+    p.add_argument("--fp32", action="store_true")
+    p.add_argument("--tol", type=float, default=1e-8)
+    p.add_argument("--reps", type=int, default=20)
+    p.add_argument("--no-solve", action="store_true", help="skip the solves (multigrid and Chebyshev Jacobi)")
+    p.add_argument("--no-kernels", action="store_true", help="skip the per-kernel times")
+    p.add_argument("--max-jacobi-iters", type=int, default=200000)
+    a = p.parse_args()
+    if not torch.cuda.is_available():
+        print("bench_multigrid: no GPU", file=sys.stderr)
+        return 2
+    dev = torch.device("cuda:0")
+    dt = torch.float32 if a.fp32 else torch.float64
+    rows, cols = a.rows, a.cols
+    sync = lambda: torch.cuda.synchronize(dev)  # noqa: E731
+
+    kern = None if a.no_kernels else kernel_times(rows, cols, dt, a.reps, dev)
+
+    # one V-cycle: host clock around cycle() (it ends in the residual read)
+    mg = PoissonMultigrid(rows, cols, dtype=dt, device=dev)
+    setup(mg, rows, cols)
+    for _ in range(3):
+        mg.cycle()
+    sync()
+    ts = []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        mg.cycle()
+        ts.append(time.perf_counter() - t0)
+    cycle_ms = statistics.median(ts) * 1e3
+    share = None
+    if len(mg.levels) > 2:
+        ts = []
+        for _ in range(a.reps):
+            sync()
+            t0 = time.perf_counter()
+            mg._vcycle(2)
+            sync()
+            ts.append(time.perf_counter() - t0)
+        share = statistics.median(ts) * 1e3 / cycle_ms
+
+    solve = {}
+    if not a.no_solve:
+        s = PoissonMultigrid(rows, cols, dtype=dt, device=dev)
+        setup(s, rows, cols)
+        sync()
+        t0 = time.perf_counter()
+        n = s.solve(a.tol)
+        sync()
+        solve = {"solve_ms": round((time.perf_counter() - t0) * 1e3, 3), "cycles": n, "residual": s.last_residual}
+        j = SlabJacobi(parallel.DistContext(device=dev), rows, cols, dtype=dt, check_every=100, accel="chebyshev")
+        setup(j, rows, cols)
+        j.run(200)  # warm
+        setup(j, rows, cols)
+        j.iteration = 0
+        sync()
+        t0 = time.perf_counter()
+        j.run(a.max_jacobi_iters, tol=a.tol)
+        sync()
+        solve.update({"jacobi_solve_ms": round((time.perf_counter() - t0) * 1e3, 3), "jacobi_iterations": j.iteration,
+                      "jacobi_residual": j.last_residual})
+        solve["jacobi_over_multigrid"] = round(solve["jacobi_solve_ms"] / solve["solve_ms"], 2)
+        solve["max_abs_difference"] = float((s.u - j.u).abs().max())
+
+    print(json.dumps({
+        "metric": "2-D Poisson multigrid V(2,2) cycle time on one MI355X",
+        "value": round(cycle_ms, 4), "unit": "ms/cycle", "higher_is_better": False,
+        "grid": [rows + 2, cols], "dtype": "fp32" if a.fp32 else "fp64", "levels": len(mg.levels),
+        "coarsest": list(mg.levels[-1]), "reps": a.reps, "tol": a.tol,
+        "below_level2_share": None if share is None else round(share, 3),
+        "level0_kernels": kern, **solve}), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
