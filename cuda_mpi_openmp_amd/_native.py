@@ -51,6 +51,8 @@ _SIGNATURES = {
     ),
     "mpx_conv_set_band_min": (ctypes.c_longlong, [ctypes.c_longlong]),
     "mpx_conv_set_band_mode": (c_int, [c_int]),
+    # (w, rows, k, anchor, resident, remote_rows, *seg, *opt) -> 0 wave / 1 band4 / 2 band16v
+    "mpx_conv_band_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _ip, _ip]),
     "mpx_conv_peer": (
         c_int,
         [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _fp, _fp, c_vp],

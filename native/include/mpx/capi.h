@@ -94,6 +94,18 @@ long long mpx_conv_set_band_min(long long n);
  * 3 NT stores + NT interior loads (default), 4 vertical halo sharing through LDS
  * for 5-row windows); returns the previous mode, m < 0 queries */
 int mpx_conv_set_band_mode(int m);
+/* Which kernel an mpx_conv / mpx_conv_peer launch of `rows` output rows
+ * (oy1 - oy0) of a w-wide image with a k x k window takes, given 16-byte
+ * aligned rows, a tap class with a band instantiation (every dense class;
+ * separable MAG2 / LIN1) and the current band mode and band minimum:
+ * 0 wave kernel, 1 conv_band4_kernel, 2 conv_band16v_kernel. *seg receives the
+ * rows per wave segment and *opt the kernel's OPT value (0, 2, 34, 2|2048,
+ * 34|2048: bit 11 = batched aprons, walks of at most 32 rows; 2|64 for the
+ * 16v kernel); both 0 for the wave kernel. resident: the MPX_CONV_RESIDENT
+ * hint; remote_rows: mpx_conv_peer with halo rows outside `in`. The launcher
+ * decides by the same function; host arithmetic only, no GPU needed. */
+int mpx_conv_band_plan(int w, int rows, int k, int anchor, int resident, int remote_rows,
+                       int *seg, int *opt);
 
 /* Tuning-harness entry (tools/kbench.py): kernel variants for k in {2, 5}, MAG2,
  * whole image. kind 0 = LDS streaming kernel (p1 = rows per wave 4/8/16,

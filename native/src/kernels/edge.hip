@@ -199,3 +199,12 @@ extern "C" long long mpx_conv_set_band_min(long long n) {
     if (n < 0) return mpx::edgel::g_band_min_pixels.load();
     return mpx::edgel::g_band_min_pixels.exchange(n);
 }
+
+// The plan launch_band itself follows (edgel::band_plan): host arithmetic only.
+extern "C" int mpx_conv_band_plan(int w, int rows, int k, int anchor, int resident, int remote_rows, int *seg,
+                                  int *opt) {
+    const mpx::edgel::BandPlan p = mpx::edgel::band_plan(w, rows, k, anchor, resident != 0, remote_rows != 0);
+    if (seg) *seg = p.seg;
+    if (opt) *opt = p.opt;
+    return p.kernel;
+}

@@ -223,34 +223,66 @@ struct ResidentHint {
 // strip edges on small images).
 inline constexpr int64_t kBandMinPixels = int64_t(1) << 22;
 inline std::atomic<int64_t> g_band_min_pixels{kBandMinPixels};
+// the part of band_ok that depends on the shape and the mode / threshold
+// state only (not on pointers or the pitch)
+inline bool band_shape_ok(int w, int rows) {
+    return band_mode() != 0 && w > 0 && rows > 0 &&
+           (int64_t)w * rows >= g_band_min_pixels.load(std::memory_order_relaxed) && w % 4 == 0;
+}
 inline bool band_ok(const uint32_t *in, const uint32_t *out, int w, int pitch, const edge::RowSrc &rs, int rows) {
-    return band_mode() != 0 && (int64_t)w * rows >= g_band_min_pixels.load(std::memory_order_relaxed) && w % 4 == 0 && pitch % 4 == 0 && aligned16(in) && aligned16(out) &&
+    return band_shape_ok(w, rows) && pitch % 4 == 0 && aligned16(in) && aligned16(out) &&
            (!rs.up || aligned16(rs.up)) && (!rs.dn || aligned16(rs.dn));
 }
 
+inline constexpr bool band_fits(int k, int a) { return k >= 1 && a >= 0 && a < k && a <= 2 && k - 1 - a <= 2; }
 template <int K, int A>
-inline constexpr bool kBandFits = A <= 2 && K - 1 - A <= 2;
+inline constexpr bool kBandFits = band_fits(K, A);
+
+// What a launch of `rows` output rows of a w-wide image with a K x K window
+// runs, for 16-B aligned rows and the current mode / threshold state: kernel 0
+// = wave kernel, 1 = conv_band4_kernel, 2 = conv_band16v_kernel, with the
+// segment rows and the OPT template value. The one place that decides;
+// launch_band switches on it and mpx_conv_band_plan reports it (tests aim
+// their shapes at its limits through the query).
+//   resident: the MPX_CONV_RESIDENT hint; remote: halo rows outside `in`
+struct BandPlan {
+    int kernel, seg, opt;
+};
+inline BandPlan band_plan(int w, int rows, int k, int a, bool resident, bool remote) {
+    if (!band_fits(k, a) || !band_shape_ok(w, rows)) return BandPlan{0, 0, 0};
+    const int m = band_mode();
+    if (m == 0) return BandPlan{0, 0, 0};  // (the mode switched since band_shape_ok read it)
+    if (m == 4 && k == 5 && a == 2 && !remote) return BandPlan{2, kVSeg, 2 | 64};
+    const int seg = band4_auto_seg(w, rows);
+    if (m == 1) return BandPlan{1, seg, 0};
+    // walks of at most 32 rows (every segment of a 4096^2 frame: 16 + 4) take
+    // the batched aprons (OPT bit 11: one apron load and luma per walk, two
+    // ds_bpermute per row instead of a load, a luma and two selects)
+    const bool bpa = seg + k - 1 <= 32;
+    return BandPlan{1, seg, ((m == 2 || resident) ? 2 : 34) | (bpa ? 2048 : 0)};
+}
 
 template <int K, int A, int MODE, class F>
 int launch_band(const uint32_t *in, uint32_t *out, int w, int pitch, int oy0, int oy1, int y_lo, int y_hi,
                 const Taps &taps, hipStream_t s, const edge::RowSrc &rs) {
-    const int m = band_mode();
+    const bool remote = (rs.up && rs.up != in) || (rs.dn && rs.dn != in);
+    const BandPlan p = band_plan(w, oy1 - oy0, K, A, tl_conv_resident, remote);
     if constexpr (K == 5 && A == 2) {
-        if (m == 4 && (!rs.up || rs.up == in) && (!rs.dn || rs.dn == in))
-            return launch_band16v<K, A, MODE, true, F>(in, out, w, pitch, oy0, oy1, y_lo, y_hi, taps, s);
+        if (p.kernel == 2) return launch_band16v<K, A, MODE, true, F>(in, out, w, pitch, oy0, oy1, y_lo, y_hi, taps, s);
     }
-    if (m == 1)
-        return launch_band4<K, A, MODE, true, F, 0>(in, out, w, pitch, oy0, oy1, y_lo, y_hi, taps, s, 0, rs);
-    // walks of at most 32 rows (every segment of a 4096^2 frame: 16 + 4) take
-    // the batched aprons (OPT bit 11: one apron load and luma per walk, two
-    // ds_bpermute per row instead of a load, a luma and two selects)
-    const int seg = band4_auto_seg(w, oy1 - oy0);
-    const bool bpa = seg + K - 1 <= 32;
-    if (m == 2 || tl_conv_resident)
-        return bpa ? launch_band4<K, A, MODE, true, F, 2 | 2048>(in, out, w, pitch, oy0, oy1, y_lo, y_hi, taps, s, seg, rs)
-                   : launch_band4<K, A, MODE, true, F, 2>(in, out, w, pitch, oy0, oy1, y_lo, y_hi, taps, s, seg, rs);
-    return bpa ? launch_band4<K, A, MODE, true, F, 34 | 2048>(in, out, w, pitch, oy0, oy1, y_lo, y_hi, taps, s, seg, rs)
-               : launch_band4<K, A, MODE, true, F, 34>(in, out, w, pitch, oy0, oy1, y_lo, y_hi, taps, s, seg, rs);
+    MPX_CHECK_ARG(p.kernel == 1, "band kernel: the launch shape does not plan onto it");
+    switch (p.opt) {
+        case 0:
+            return launch_band4<K, A, MODE, true, F, 0>(in, out, w, pitch, oy0, oy1, y_lo, y_hi, taps, s, p.seg, rs);
+        case 2 | 2048:
+            return launch_band4<K, A, MODE, true, F, 2 | 2048>(in, out, w, pitch, oy0, oy1, y_lo, y_hi, taps, s, p.seg, rs);
+        case 2:
+            return launch_band4<K, A, MODE, true, F, 2>(in, out, w, pitch, oy0, oy1, y_lo, y_hi, taps, s, p.seg, rs);
+        case 34 | 2048:
+            return launch_band4<K, A, MODE, true, F, 34 | 2048>(in, out, w, pitch, oy0, oy1, y_lo, y_hi, taps, s, p.seg, rs);
+        default:
+            return launch_band4<K, A, MODE, true, F, 34>(in, out, w, pitch, oy0, oy1, y_lo, y_hi, taps, s, p.seg, rs);
+    }
 }
 
 // Named filters whose taps are compiled in (zero taps disappear); selected
