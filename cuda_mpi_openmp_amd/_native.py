@@ -125,6 +125,29 @@ _SIGNATURES = {
     "mpx_jacobi3d_tile": (c_int, [c_int, c_int, c_int, _ip]),
     "mpx_cpu_jacobi3d_f64": (ctypes.c_double, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int]),
     "mpx_cpu_jacobi3d_accel_f64": (ctypes.c_double, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.c_double]),
+    # 3-D multigrid: relax (u, b or NULL, un, d, ny, nx, pitch, plane, k0, k1, omega, resid, stream),
+    # residual (u, b or NULL, r, d, ny, nx, pitch_u, plane_u, pitch_b, plane_b, pitch_r, plane_r, resid, stream),
+    # restrict (r, bc, dc, hc, wc, pitch_r, plane_r, pitch_bc, plane_bc, stream),
+    # prolong_add (e, u, dc, hc, wc, pitch_e, plane_e, pitch_u, plane_u, stream); plane strides are int64
+    "mpx_jacobi3d_relax_f64": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_int,
+                                       ctypes.c_double, c_vp, c_vp]),
+    "mpx_jacobi3d_relax_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_int,
+                                       ctypes.c_double, c_vp, c_vp]),
+    "mpx_mg3_residual_f64": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64, c_int, c_i64,
+                                     c_vp, c_vp]),
+    "mpx_mg3_residual_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64, c_int, c_i64,
+                                     c_vp, c_vp]),
+    "mpx_mg3_restrict_f64": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64, c_vp]),
+    "mpx_mg3_restrict_f32": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64, c_vp]),
+    "mpx_mg3_prolong_add_f64": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64, c_vp]),
+    "mpx_mg3_prolong_add_f32": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64, c_vp]),
+    "mpx_mg3_walk": (c_int, [_ip]),
+    "mpx_cpu_jacobi3d_relax_f64": (ctypes.c_double, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_int,
+                                                     ctypes.c_double]),
+    "mpx_cpu_mg3_residual_f64": (ctypes.c_double, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64,
+                                                   c_int, c_i64]),
+    "mpx_cpu_mg3_restrict_f64": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64]),
+    "mpx_cpu_mg3_prolong_add_f64": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64]),
     "mpx_cpu_threads": (c_int, []),
     "mpx_cpu_vsub_f64": (None, [c_vp, c_vp, c_vp, c_i64]),
     "mpx_cpu_vsub_f32": (None, [c_vp, c_vp, c_vp, c_i64]),

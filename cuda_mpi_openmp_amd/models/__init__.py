@@ -7,6 +7,7 @@ form and a row/shard-decomposed multi-GPU form:
   stencil  SlabJacobi                          2-D Jacobi with halo exchange
   stencil  SlabJacobi3D                        3-D Jacobi on plane slabs
   stencil  PoissonMultigrid                    2-D Poisson by geometric multigrid V-cycles (one device)
+  stencil  PoissonMultigrid3D                  3-D Poisson in a box by geometric multigrid V-cycles (one device)
 """
 
 from .classifier import PixelClassifier, SlabPixelClassifier
@@ -14,7 +15,8 @@ from .edge import EdgeDetector, SlabEdgeDetector
 from .jacobi import SlabJacobi
 from .jacobi3d import SlabJacobi3D
 from .multigrid import PoissonMultigrid
+from .multigrid3d import PoissonMultigrid3D
 from .vector import ShardedVectorSub, VectorSub
 
 __all__ = ["PixelClassifier", "SlabPixelClassifier", "EdgeDetector", "SlabEdgeDetector", "SlabJacobi", "SlabJacobi3D",
-           "PoissonMultigrid", "ShardedVectorSub", "VectorSub"]
+           "PoissonMultigrid", "PoissonMultigrid3D", "ShardedVectorSub", "VectorSub"]

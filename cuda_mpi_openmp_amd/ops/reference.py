@@ -235,3 +235,77 @@ def mg_prolong_add(e: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
     out = u.clone()
     out[1:-1, 1:-1] = u[1:-1, 1:-1] + add[1:-1, 1:-1]
     return out
+
+
+def mg3_residual(u: torch.Tensor, rhs: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """3-D multigrid residual in u's own dtype, in the kernels' association:
+    r = ((((zm + zp) + (ym + yp)) + (xm + xp)) [+ b]) - 6 c at the interior
+    points of a (D, H, W) grid. Every other element of the result is ``out``'s
+    (zeros without ``out``): the kernels leave r's boundary alone."""
+    u = u.cpu()
+    if u.dim() != 3:
+        raise ValueError("u must be a (D, H, W) tensor")
+    r = torch.zeros_like(u) if out is None else out.cpu().to(u.dtype).clone()
+    c = slice(1, -1)
+    n = ((u[:-2, c, c] + u[2:, c, c]) + (u[c, :-2, c] + u[c, 2:, c])) + (u[c, c, :-2] + u[c, c, 2:])
+    if rhs is not None:
+        b = rhs.cpu().to(u.dtype)
+        if b.shape != u.shape:
+            raise ValueError("rhs must have u's shape")
+        n = n + b[c, c, c]
+    r[c, c, c] = n - u[c, c, c] * 6.0
+    return r
+
+
+def mg3_restrict(r: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """27-point full weighting of a fine (2 Dc - 1, 2 Hc - 1, 2 Wc - 1) residual
+    into the coarse interior, scaled for the h^2-scaled coarse right-hand side,
+    in r's dtype and the kernels' separable association: P_k is ``mg_restrict``'s
+    2-D rule in fine plane k, bc[K] = (P_2K + (P_2K-1 + P_2K+1) * 0.5) * 0.5,
+    every operation rounded. Every other element of the (Dc, Hc, Wc) result is
+    ``out``'s (zeros without ``out``)."""
+    r = r.cpu()
+    if r.dim() != 3 or any(s % 2 == 0 or s < 3 for s in r.shape):
+        raise ValueError("fine grid must be (2 Dc - 1, 2 Hc - 1, 2 Wc - 1)")
+    dc, hc, wc = ((s + 1) // 2 for s in r.shape)
+    bc = torch.zeros((dc, hc, wc), dtype=r.dtype) if out is None else out.cpu().to(r.dtype).clone()
+    if bc.shape != (dc, hc, wc):
+        raise ValueError("out must be the coarse grid")
+    if dc < 3 or hc < 3 or wc < 3:
+        return bc
+    c, up, dn = slice(2, -2, 2), slice(1, -3, 2), slice(3, -1, 2)
+    q = r[1:-1]  # fine planes 1 .. D - 2: P[k - 1] is P_k
+    e = (q[:, up, c] + q[:, dn, c]) + (q[:, c, up] + q[:, c, dn])
+    d = (q[:, up, up] + q[:, up, dn]) + (q[:, dn, up] + q[:, dn, dn])
+    P = (q[:, c, c] + e * 0.5) + d * 0.25
+    bc[1:-1, 1:-1, 1:-1] = (P[1:-1:2] + (P[0:-2:2] + P[2::2]) * 0.5) * 0.5
+    return bc
+
+
+def mg3_prolong_add(e: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+    """u plus the trilinear interpolation of the coarse e at u's interior, in u's
+    dtype and the kernels' association: unscaled pair sums in z, then y, then x,
+    and one exact scale 0.5^(number of odd coordinates), with no multiply where
+    it is 1; u's boundary is returned unchanged."""
+    u = u.cpu()
+    e = e.cpu().to(u.dtype)
+    dc, hc, wc = e.shape
+    if u.shape != (2 * dc - 1, 2 * hc - 1, 2 * wc - 1):
+        raise ValueError("u must be (2 Dc - 1, 2 Hc - 1, 2 Wc - 1)")
+    Z = torch.zeros((u.shape[0], hc, wc), dtype=u.dtype)
+    Z[0::2] = e
+    Z[1::2] = e[:-1] + e[1:]
+    Y = torch.zeros((u.shape[0], u.shape[1], wc), dtype=u.dtype)
+    Y[:, 0::2] = Z
+    Y[:, 1::2] = Z[:, :-1] + Z[:, 1:]
+    X = torch.zeros_like(u)
+    X[:, :, 0::2] = Y
+    X[:, :, 1::2] = Y[:, :, :-1] + Y[:, :, 1:]
+    for oz in (0, 1):
+        for oy in (0, 1):
+            for ox in (0, 1):
+                if oz + oy + ox:
+                    X[oz::2, oy::2, ox::2] *= 0.5 ** (oz + oy + ox)
+    out = u.clone()
+    out[1:-1, 1:-1, 1:-1] = u[1:-1, 1:-1, 1:-1] + X[1:-1, 1:-1, 1:-1]
+    return out

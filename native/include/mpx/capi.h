@@ -430,6 +430,75 @@ int mpx_jacobi3d_accel_f32(const float *u, const float *b, float *un, int nx, in
  * tile is 1. out: 4 ints. */
 int mpx_jacobi3d_tile(int fp64, int rhs, int accel, int *out);
 
+/* 3-D geometric multigrid on a (D, H, W) grid, x fastest, with Dirichlet values
+ * on all six faces (native/src/kernels/multigrid3d.hip). Every buffer is
+ * pitched: unit element stride in x, a row pitch >= W and a plane stride >=
+ * H * pitch, both in elements; plane offsets are 64-bit; padding is never read
+ * for a result and never written. The coarse grid of (D, H, W) is (dc, hc, wc)
+ * with D = 2 dc - 1, H = 2 hc - 1, W = 2 wc - 1; coarse (K, J, I) sits on fine
+ * (2K, 2J, 2I). The discrete equation is 6 u - (sum of the six neighbours) = b,
+ * b = h^2 f. Every + - * is one rounded operation in the buffer type, never an
+ * FMA, so fp32, fp64, the CPU references and a dtype-preserving expression
+ * agree bit for bit. 16-byte aligned bases with pitches and plane strides that
+ * are multiples of the 16-byte vector take the vector kernels, everything else
+ * the per-element kernels. Null pointers and bad geometry: MPX_ERR_ARG, nothing
+ * written. With n = ((zm + zp) + (ym + yp)) + (xm + xp) [+ b] (b NULL: no "+ b")
+ * and c the centre value:
+ *
+ * jacobi3d_relax (the damped sweep over planes [k0, k1), 1 <= k0 <= k1 <= d - 1;
+ *   empty: no-op): s = n * (T)(1.0 / 6.0), exactly mpx_jacobi3d_*'s s; interior
+ *   points get un = c + omega * (s - c), three rounded operations, omega rounded
+ *   once to T (finite and positive before and after that rounding: otherwise
+ *   MPX_ERR_ARG and nothing is written). Boundary rows and columns of a swept
+ *   plane copy through; other planes are not written; un is output only. resid
+ *   (nullable, zeroed by the caller) receives max|s - c| as the sweeps fold
+ *   theirs. u, b and un share one pitch and one plane stride.
+ * mg3_residual: r = n - (T)6 * c at the interior points; r's boundary is not
+ *   written; resid (nullable, zeroed by the caller) receives max|r|. d, ny,
+ *   nx >= 3.
+ * mg3_restrict (27-point full weighting, scaled for the h^2-scaled coarse
+ *   right-hand side, defined separably): for each fine plane k, P_k[J][I] is the
+ *   2-D rule of mg_restrict above applied in the plane, with i = 2J, j = 2I:
+ *     e = (r[k][i-1][j] + r[k][i+1][j]) + (r[k][i][j-1] + r[k][i][j+1])
+ *     d = (r[k][i-1][j-1] + r[k][i-1][j+1]) + (r[k][i+1][j-1] + r[k][i+1][j+1])
+ *     P_k[J][I] = (r[k][i][j] + e * 0.5) + d * 0.25
+ *   then bc[K][J][I] = (P_2K + (P_2K-1 + P_2K+1) * 0.5) * 0.5 at the coarse
+ *   interior (weights: centre 0.5, face 0.25, edge 0.125, corner 0.0625). bc's
+ *   boundary is not written; r's boundary is not read for a result; without a
+ *   coarse interior (dc, hc or wc < 3) the call is a no-op. dc, hc, wc >= 2.
+ * mg3_prolong_add (trilinear interpolation added to u's interior, in place):
+ *   unscaled pair sums in z, then y, then x, and one exact scale:
+ *     Z[k]       = e[K] for k = 2K,        e[K] + e[K+1] for k = 2K + 1
+ *     Y[k][i]    = Z[k][J] for i = 2J,     Z[k][J] + Z[k][J+1] for i = 2J + 1
+ *     X[k][i][j] = Y[k][i][I] for j = 2I,  Y[k][i][I] + Y[k][i][I+1] for j = 2I + 1
+ *     u[k][i][j] += X[k][i][j] * 0.5^(number of odd coordinates among k, i, j)
+ *   with no multiply when that factor is 1. e's boundary is read; u's boundary
+ *   is not written. dc, hc, wc >= 2. */
+int mpx_jacobi3d_relax_f64(const double *u, const double *b, double *un, int d, int ny, int nx, int pitch,
+                           int64_t plane, int k0, int k1, double omega, double *resid, void *stream);
+int mpx_jacobi3d_relax_f32(const float *u, const float *b, float *un, int d, int ny, int nx, int pitch, int64_t plane,
+                           int k0, int k1, double omega, float *resid, void *stream);
+int mpx_mg3_residual_f64(const double *u, const double *b, double *r, int d, int ny, int nx, int pitch_u,
+                         int64_t plane_u, int pitch_b, int64_t plane_b, int pitch_r, int64_t plane_r, double *resid,
+                         void *stream);
+int mpx_mg3_residual_f32(const float *u, const float *b, float *r, int d, int ny, int nx, int pitch_u, int64_t plane_u,
+                         int pitch_b, int64_t plane_b, int pitch_r, int64_t plane_r, float *resid, void *stream);
+int mpx_mg3_restrict_f64(const double *r, double *bc, int dc, int hc, int wc, int pitch_r, int64_t plane_r,
+                         int pitch_bc, int64_t plane_bc, void *stream);
+int mpx_mg3_restrict_f32(const float *r, float *bc, int dc, int hc, int wc, int pitch_r, int64_t plane_r, int pitch_bc,
+                         int64_t plane_bc, void *stream);
+int mpx_mg3_prolong_add_f64(const double *e, double *u, int dc, int hc, int wc, int pitch_e, int64_t plane_e,
+                            int pitch_u, int64_t plane_u, void *stream);
+int mpx_mg3_prolong_add_f32(const float *e, float *u, int dc, int hc, int wc, int pitch_e, int64_t plane_e, int pitch_u,
+                            int64_t plane_u, void *stream);
+/* The walks of the 3-D multigrid launches: out[0] = rows of a plane walked per
+ * lane by relax / residual, out[1] / out[2] = coarse planes walked per lane by
+ * the restriction / the prolongation, out[3] = the wave count below which a
+ * launch halves its walk until it has that many waves or the walk is 1,
+ * out[4] = waves per workgroup (row blocks of the stencil walk, coarse rows of
+ * the transfers). out: 5 ints. */
+int mpx_mg3_walk(int *out);
+
 /* ---------------- lab5: ascending sort (no reference program) ---------------- */
 /* In place on the device; dtype is an mpx_sort_dtype. int32/float32: LSD radix sort
  * (onesweep, 8-bit digits) on order-preserving uint32 keys, bitonic network for
@@ -502,6 +571,18 @@ int mpx_cpu_mg_prolong_add_f64(const double *e, double *u, int hc, int wc, int p
 double mpx_cpu_jacobi3d_f64(const double *u, const double *b, double *un, int nx, int ny, int k0, int k1);
 double mpx_cpu_jacobi3d_accel_f64(const double *u, const double *b, double *un, int nx, int ny, int k0, int k1,
                                   double omega);
+/* the 3-D multigrid operators of mpx_jacobi3d_relax_f64 / mpx_mg3_*_f64. relax
+ * and residual return the residual (NaN, with nothing written, on a null
+ * pointer, bad geometry or a bad omega); restrict and prolong_add return 0, or
+ * -1, with nothing written, on bad arguments */
+double mpx_cpu_jacobi3d_relax_f64(const double *u, const double *b, double *un, int d, int ny, int nx, int pitch,
+                                  int64_t plane, int k0, int k1, double omega);
+double mpx_cpu_mg3_residual_f64(const double *u, const double *b, double *r, int d, int ny, int nx, int pitch_u,
+                                int64_t plane_u, int pitch_b, int64_t plane_b, int pitch_r, int64_t plane_r);
+int mpx_cpu_mg3_restrict_f64(const double *r, double *bc, int dc, int hc, int wc, int pitch_r, int64_t plane_r,
+                             int pitch_bc, int64_t plane_bc);
+int mpx_cpu_mg3_prolong_add_f64(const double *e, double *u, int dc, int hc, int wc, int pitch_e, int64_t plane_e,
+                                int pitch_u, int64_t plane_u);
 void mpx_cpu_sort(void *data, int64_t n, int dtype);
 void mpx_cpu_sort_pairs(void *keys, uint32_t *vals, int64_t n, int dtype, int flags);
 

@@ -622,6 +622,166 @@ double mpx_cpu_jacobi3d_accel_f64(const double *u, const double *b, double *un, 
     return jacobi3d_planes(u, b, un, nx, ny, k0, k1, &omega);
 }
 
+/* 3-D multigrid operators on a pitched (D, H, W) grid (row pitch and 64-bit
+ * plane stride in elements) with Dirichlet values on all six faces, and its
+ * coarse grid (dc, hc, wc), D = 2 dc - 1, H = 2 hc - 1, W = 2 wc - 1 (capi.h);
+ * every operation rounded (-ffp-contract=off), in the GPU kernels' order. */
+static int mg3_strides_ok(int h, int w, int pitch, int64_t plane) {
+    return pitch >= w && plane >= (int64_t)h * pitch;
+}
+
+static int mg3_coarse_ok(int dc, int hc, int wc) {
+    return dc >= 2 && hc >= 2 && wc >= 2 && dc < (1 << 29) && hc < (1 << 29) && wc < (1 << 29);
+}
+
+/* n = ((zm + zp) + (ym + yp)) + (xm + xp) around row pointer c, column x */
+static inline double mg3_neighbours(const double *c, int x, int pitch, int64_t plane) {
+    return ((c[x - plane] + c[x + plane]) + (c[x - pitch] + c[x + pitch])) + (c[x - 1] + c[x + 1]);
+}
+
+/* Damped 3-D sweep over planes [k0, k1): un = c + omega * (s - c) at the
+ * interior points, boundary rows and columns of a swept plane copied through,
+ * un output only; returns max|s - c|. u, b and un share pitch and plane stride. */
+double mpx_cpu_jacobi3d_relax_f64(const double *u, const double *b, double *un, int d, int ny, int nx, int pitch,
+                                  int64_t plane, int k0, int k1, double omega) {
+    const double sixth = 1.0 / 6.0;
+    double res = 0.0;
+    int k;
+    if (!u || !un || nx < 3 || ny < 3 || d < 3 || k0 < 1 || k1 < k0 || k1 > d - 1 || !mg3_strides_ok(ny, nx, pitch, plane) ||
+        !(omega > 0.0) || !isfinite(omega))
+        return NAN;
+#pragma omp parallel for schedule(static) reduction(max : res)
+    for (k = k0; k < k1; ++k) {
+        for (int y = 0; y < ny; ++y) {
+            const int64_t off = (int64_t)k * plane + (int64_t)y * pitch;
+            const double *c = u + off;
+            double *o = un + off;
+            if (y == 0 || y == ny - 1) {
+                for (int x = 0; x < nx; ++x) o[x] = c[x];
+                continue;
+            }
+            o[0] = c[0];
+            o[nx - 1] = c[nx - 1];
+            for (int x = 1; x < nx - 1; ++x) {
+                const double n = mg3_neighbours(c, x, pitch, plane);
+                const double s = b ? (n + b[off + x]) * sixth : n * sixth;
+                const double df = s - c[x];
+                const double a = fabs(df);
+                res = a > res ? a : res;
+                const double t = omega * df;
+                o[x] = c[x] + t;
+            }
+        }
+    }
+    return res;
+}
+
+double mpx_cpu_mg3_residual_f64(const double *u, const double *b, double *r, int d, int ny, int nx, int pitch_u,
+                                int64_t plane_u, int pitch_b, int64_t plane_b, int pitch_r, int64_t plane_r) {
+    double res = 0.0;
+    int k;
+    if (!u || !r || nx < 3 || ny < 3 || d < 3 || !mg3_strides_ok(ny, nx, pitch_u, plane_u) ||
+        !mg3_strides_ok(ny, nx, pitch_r, plane_r) || (b && !mg3_strides_ok(ny, nx, pitch_b, plane_b)))
+        return NAN;
+#pragma omp parallel for schedule(static) reduction(max : res)
+    for (k = 1; k < d - 1; ++k) {
+        for (int y = 1; y < ny - 1; ++y) {
+            const double *c = u + (int64_t)k * plane_u + (int64_t)y * pitch_u;
+            const double *bb = b ? b + (int64_t)k * plane_b + (int64_t)y * pitch_b : NULL;
+            double *o = r + (int64_t)k * plane_r + (int64_t)y * pitch_r;
+            for (int x = 1; x < nx - 1; ++x) {
+                double n = mg3_neighbours(c, x, pitch_u, plane_u);
+                if (bb) n = n + bb[x];
+                const double c6 = 6.0 * c[x];
+                const double v = n - c6;
+                const double a = fabs(v);
+                res = a > res ? a : res;
+                o[x] = v;
+            }
+        }
+    }
+    return res;
+}
+
+/* P_k[J][I]: the 2-D full weighting of fine plane k (pointer to its row 2J) */
+static inline double mg3_plane_weight(const double *m, int j, int pitch) {
+    const double *t = m - pitch, *dn = m + pitch;
+    const double e = (t[j] + dn[j]) + (m[j - 1] + m[j + 1]);
+    const double x = (t[j - 1] + t[j + 1]) + (dn[j - 1] + dn[j + 1]);
+    const double eh = e * 0.5;
+    const double xq = x * 0.25;
+    return (m[j] + eh) + xq;
+}
+
+int mpx_cpu_mg3_restrict_f64(const double *r, double *bc, int dc, int hc, int wc, int pitch_r, int64_t plane_r,
+                             int pitch_bc, int64_t plane_bc) {
+    int K;
+    if (!r || !bc || !mg3_coarse_ok(dc, hc, wc) || !mg3_strides_ok(2 * hc - 1, 2 * wc - 1, pitch_r, plane_r) ||
+        !mg3_strides_ok(hc, wc, pitch_bc, plane_bc))
+        return -1;
+    if (dc < 3 || hc < 3 || wc < 3) return 0; /* no coarse interior */
+#pragma omp parallel for schedule(static)
+    for (K = 1; K < dc - 1; ++K) {
+        for (int J = 1; J < hc - 1; ++J) {
+            const double *m = r + (int64_t)(2 * K) * plane_r + (int64_t)(2 * J) * pitch_r;
+            double *o = bc + (int64_t)K * plane_bc + (int64_t)J * pitch_bc;
+            for (int I = 1; I < wc - 1; ++I) {
+                const double lo = mg3_plane_weight(m - plane_r, 2 * I, pitch_r);
+                const double mid = mg3_plane_weight(m, 2 * I, pitch_r);
+                const double hi = mg3_plane_weight(m + plane_r, 2 * I, pitch_r);
+                const double z = lo + hi;
+                const double zh = z * 0.5;
+                const double v = mid + zh;
+                o[I] = v * 0.5;
+            }
+        }
+    }
+    return 0;
+}
+
+int mpx_cpu_mg3_prolong_add_f64(const double *e, double *u, int dc, int hc, int wc, int pitch_e, int64_t plane_e,
+                                int pitch_u, int64_t plane_u) {
+    int k;
+    if (!e || !u || !mg3_coarse_ok(dc, hc, wc) || !mg3_strides_ok(hc, wc, pitch_e, plane_e) ||
+        !mg3_strides_ok(2 * hc - 1, 2 * wc - 1, pitch_u, plane_u))
+        return -1;
+    const int d = 2 * dc - 1, h = 2 * hc - 1, w = 2 * wc - 1;
+    static const double scale[4] = {1.0, 0.5, 0.25, 0.125};
+#pragma omp parallel for schedule(static)
+    for (k = 1; k < d - 1; ++k) {
+        const int64_t dz = (k & 1) ? plane_e : 0; /* the +1 neighbours are read on odd coordinates only */
+        for (int i = 1; i < h - 1; ++i) {
+            const int64_t dy = (i & 1) ? pitch_e : 0;
+            const double *c = e + (int64_t)(k / 2) * plane_e + (int64_t)(i / 2) * pitch_e;
+            double *o = u + (int64_t)k * plane_u + (int64_t)i * pitch_u;
+            for (int j = 1; j < w - 1; ++j) {
+                const int I = j / 2;
+                const int odd = (k & 1) + (i & 1) + (j & 1);
+                /* z pair sums at the (up to) four coarse (row, column) corners, then y, then x */
+                double z00 = c[I], z10 = c[I + dy], y0, y1 = 0.0, x;
+                if (k & 1) {
+                    z00 = z00 + c[I + dz];
+                    z10 = z10 + c[I + dy + dz];
+                }
+                y0 = (i & 1) ? z00 + z10 : z00;
+                if (j & 1) {
+                    double z01 = c[I + 1], z11 = c[I + 1 + dy];
+                    if (k & 1) {
+                        z01 = z01 + c[I + 1 + dz];
+                        z11 = z11 + c[I + 1 + dy + dz];
+                    }
+                    y1 = (i & 1) ? z01 + z11 : z01;
+                    x = y0 + y1;
+                } else {
+                    x = y0;
+                }
+                o[j] = odd ? o[j] + x * scale[odd] : o[j] + x;
+            }
+        }
+    }
+    return 0;
+}
+
 /* Host statistics with the reference's exact operation order
  * (reference lab3/src/main.cu:102-152): mean, unbiased covariance, cofactor
  * determinant and the modular-index adjugate inverse. */

@@ -24,7 +24,7 @@
 //     and pitches that are not 16-byte multiples, as jacobi_kernel<T, false>;
 //   * every + - * is one rounded operation (-ffp-contract=off), in the order
 //     written in capi.h; the factors 4, 0.5 and 0.25 are exact.
-#include "jacobi_wave.hpp"
+#include "mg_lane.hpp"
 
 namespace mpx {
 namespace {
@@ -40,59 +40,6 @@ inline int mg_rows_per_lane(int lanes, int rows, int most) {
     int r = most;
     while (r > 1 && waves_x * ((rows + r - 1) / r) < kMgMinWaves) r >>= 1;
     return r;
-}
-
-// elements [j0, j0 + N) of a row of `cols` elements, 0 past its end: one 16-B
-// load when the whole vector lies inside the row (VEC: row + j0 is 16-B aligned)
-template <typename T, bool VEC, int N>
-__device__ __forceinline__ void load_n(const T *row, int j0, int cols, T (&dst)[N]) {
-    if constexpr (VEC) {
-        static_assert(N == JVec<T>::n, "one 16-byte vector");
-        if (j0 + N <= cols) {
-            const typename JVec<T>::type q = *reinterpret_cast<const typename JVec<T>::type *>(row + j0);
-#pragma unroll
-            for (int k = 0; k < N; ++k) dst[k] = lane_of<T>(q, k);
-            return;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < N; ++k) dst[k] = (j0 + k < cols) ? row[j0 + k] : (T)0;
-}
-
-// stores the elements of [j0, j0 + N) that lie in the columns [lo, hi]; one
-// 16-B store when all do
-template <typename T, bool VEC, int N>
-__device__ __forceinline__ void store_n(T *row, int j0, int lo, int hi, const T (&v)[N]) {
-    if constexpr (VEC) {
-        if (j0 >= lo && j0 + N - 1 <= hi) {
-            if constexpr (JVec<T>::n == 2)
-                *reinterpret_cast<double2 *>(row + j0) = make_double2(v[0], v[1]);
-            else
-                *reinterpret_cast<float4 *>(row + j0) = make_float4(v[0], v[1], v[2], v[3]);
-            return;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-        if (j0 + k >= lo && j0 + k <= hi) row[j0 + k] = v[k];
-}
-
-// row[j0 - 1], the last element of the lane to the left (`last` is this
-// lane's): a DPP wave shift; lane 0 of a wave loads it. Called by whole waves.
-template <typename T>
-__device__ __forceinline__ T from_left(T last, const T *row, int j0, int cols) {
-    T v = dpp_shift<T>(last, 0x138);
-    if ((threadIdx.x & 63) == 0) v = (j0 > 0 && j0 - 1 < cols) ? row[j0 - 1] : (T)0;
-    return v;
-}
-
-// row[jn], the first element of the lane to the right (`first` is this lane's,
-// jn the column after this lane's last); lane 63 of a wave loads it
-template <typename T>
-__device__ __forceinline__ T from_right(T first, const T *row, int jn, int cols) {
-    T v = dpp_shift<T>(first, 0x130);
-    if ((threadIdx.x & 63) == 63) v = jn < cols ? row[jn] : (T)0;
-    return v;
 }
 
 // r = ((((up + dn) + (l + rt)) [+ b]) - 4 c) at the interior points of an
@@ -256,15 +203,6 @@ __global__ __launch_bounds__(256) void mg_prolong_kernel(const T *__restrict__ e
 #pragma unroll
         for (int k = 0; k <= NV; ++k) cur[k] = nxt[k];
     }
-}
-
-template <typename T>
-bool mg_vec(std::initializer_list<const void *> ptrs, std::initializer_list<int> pitches) {
-    for (const void *p : ptrs)
-        if (p && !aligned16(p)) return false;
-    for (int p : pitches)
-        if (p % JVec<T>::n) return false;
-    return true;
 }
 
 template <typename T>

@@ -1,0 +1,183 @@
+#!/usr/bin/env python3
+"""Geometric multigrid V-cycle for the 3-D Poisson problem on one MI355X
+(models.PoissonMultigrid3D): the time of one V(2,2) cycle, the per-kernel times
+at level 0, the solve to a tolerance, and the Chebyshev-accelerated
+SlabJacobi3D solve of the same problem in the same session.
+
+  python tools/bench_multigrid3d.py [--planes 255] [--ny 257] [--nx 257] [--fp32]
+                                    [--tol 1e-8] [--reps 20] [--no-solve] [--no-kernels]
+
+Per-kernel times: device events around single launches, median over --reps
+launches that rotate through buffer sets larger than the 256 MiB Infinity
+Cache together, so no launch finds its input cached. The rates count the words
+the algorithm needs per fine point: relax 3, residual 3, restrict 1 + 1/8,
+prolong-add 2 + 1/8. ``rhs_sweep_even`` is ops.jacobi3d_sweep(rhs=) on the
+contiguous (planes + 1, ny - 1, nx - 1) grid, whose even width takes the
+wave-strip kernel: the yardstick for ``relax``. ``below_level2_share`` is the
+time of the sub-cycle from level 2 down over the whole cycle. ``walk`` is
+ops.mg3_walk() (MPX_MG3_WALK="rows,restrict_planes,prolong_planes,min_waves"
+replaces it for A/B runs).
+
+Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from cuda_mpi_openmp_amd import ops, parallel  # noqa: E402
+from cuda_mpi_openmp_amd.models import PoissonMultigrid3D, SlabJacobi3D  # noqa: E402
+
+MALL_BYTES = 256 << 20
+
+
+def problem_rhs(planes: int, ny: int, nx: int) -> torch.Tensor:
+    g = torch.Generator(device="cpu").manual_seed(11)
+    return (torch.rand((planes, ny, nx), generator=g, dtype=torch.float64) * 2.0 - 1.0) * 0.01
+
+
+def setup(sol, rhs):
+    sol.set_boundary(z0=1.0)
+    sol.fill(seed=3)
+    sol.set_rhs(tensor=rhs)
+
+
+def median_us(launch, nsets: int, reps: int, dev) -> float:
+    """Median device time of launch(k), k rotating through the buffer sets."""
+    for k in range(nsets):  # warm every set: code objects, page tables
+        launch(k)
+    torch.cuda.synchronize(dev)
+    pairs = []
+    for i in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        launch(i % nsets)
+        e1.record()
+        pairs.append((e0, e1))
+    torch.cuda.synchronize(dev)
+    return statistics.median(a.elapsed_time(b) for a, b in pairs) * 1e3
+
+
+def kernel_times(planes, ny, nx, dt, reps, dev):
+    d, h, w = planes + 2, ny, nx
+    es = 4 if dt == torch.float32 else 8
+    shapes = PoissonMultigrid3D.level_shapes(planes, ny, nx, 2)
+    nsets = max(2, -(-2 * MALL_BYTES // (d * h * w * es)))
+    sets = [PoissonMultigrid3D(planes, ny, nx, dtype=dt, device=dev, max_levels=2) for _ in range(nsets)]
+    for s in sets:  # the times do not depend on the values
+        for lv in s._lv:
+            for t in (lv.u, lv.b, lv.r):
+                if t is not None:
+                    t.uniform_(-1.0, 1.0)
+    out, pts = {}, (d - 2) * (h - 2) * (w - 2)
+    f = [s._lv[0] for s in sets]
+    out["relax"] = (median_us(lambda k: ops.jacobi3d_relax(f[k].u, f[k].un, 1, d - 1, 6.0 / 7.0, rhs=f[k].b), nsets, reps,
+                              dev), 3)
+    r = [lv.r if lv.r is not None else lv.un for lv in f]  # a single level keeps no r: any grid serves as output
+    out["residual"] = (median_us(lambda k: ops.mg3_residual(f[k].u, r[k], rhs=f[k].b), nsets, reps, dev), 3)
+    if len(shapes) == 2:
+        c = [s._lv[1] for s in sets]
+        out["restrict"] = (median_us(lambda k: ops.mg3_restrict(f[k].r, c[k].b), nsets, reps, dev), 1.125)
+        out["prolong_add"] = (median_us(lambda k: ops.mg3_prolong_add_(c[k].u, f[k].u), nsets, reps, dev), 2.125)
+    del sets, f
+    de, he, we = d - 1, h - 1, w - 1  # the even box next to it: the wave-strip kernel
+    ev = [[torch.rand((de, he, we), dtype=dt, device=dev) for _ in range(3)] for _ in range(nsets)]
+    out["rhs_sweep_even"] = (median_us(lambda k: ops.jacobi3d_sweep(ev[k][0], ev[k][1], 1, de - 1, rhs=ev[k][2]), nsets,
+                                       reps, dev), 3)
+    res = {}
+    for name, (us, words) in out.items():
+        n = (de - 2) * (he - 2) * (we - 2) if name == "rhs_sweep_even" else pts
+        res[name] = {"us": round(us, 2), "TBps": round(words * n * es / (us * 1e-6) / 1e12, 3)}
+    return res
+
+
+def main() -> int:
+    p = argparse.ArgumentParser()
+    p.add_argument("--planes", type=int, default=255)
+    p.add_argument("--ny", type=int, default=257)
+    p.add_argument("--nx", type=int, default=257)
+    p.add_argument("--fp32", action="store_true")
+    p.add_argument("--tol", type=float, default=1e-8)
+    p.add_argument("--reps", type=int, default=20)
+    p.add_argument("--no-solve", action="store_true", help="skip the solves (multigrid and Chebyshev Jacobi)")
+    p.add_argument("--no-kernels", action="store_true", help="skip the per-kernel times")
+    p.add_argument("--no-cycle", action="store_true", help="skip the cycle time")
+    p.add_argument("--max-jacobi-iters", type=int, default=100000)
+    a = p.parse_args()
+    if not torch.cuda.is_available():
+        print("bench_multigrid3d: no GPU", file=sys.stderr)
+        return 2
+    dev = torch.device("cuda:0")
+    dt = torch.float32 if a.fp32 else torch.float64
+    planes, ny, nx = a.planes, a.ny, a.nx
+    sync = lambda: torch.cuda.synchronize(dev)  # noqa: E731
+
+    kern = None if a.no_kernels else kernel_times(planes, ny, nx, dt, a.reps, dev)
+    levels = PoissonMultigrid3D.level_shapes(planes, ny, nx)
+    rhs = None if (a.no_cycle and a.no_solve) else problem_rhs(planes, ny, nx)
+
+    cycle_ms, share = None, None
+    if not a.no_cycle:
+        # one V-cycle: host clock around cycle() (it ends in the residual read)
+        mg = PoissonMultigrid3D(planes, ny, nx, dtype=dt, device=dev)
+        setup(mg, rhs)
+        for _ in range(3):
+            mg.cycle()
+        sync()
+        ts = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            mg.cycle()
+            ts.append(time.perf_counter() - t0)
+        cycle_ms = statistics.median(ts) * 1e3
+        if len(mg.levels) > 2:
+            ts = []
+            for _ in range(a.reps):
+                sync()
+                t0 = time.perf_counter()
+                mg._vcycle(2)
+                sync()
+                ts.append(time.perf_counter() - t0)
+            share = statistics.median(ts) * 1e3 / cycle_ms
+        del mg
+
+    solve = {}
+    if not a.no_solve:
+        s = PoissonMultigrid3D(planes, ny, nx, dtype=dt, device=dev)
+        setup(s, rhs)
+        sync()
+        t0 = time.perf_counter()
+        n = s.solve(a.tol)
+        sync()
+        solve = {"solve_ms": round((time.perf_counter() - t0) * 1e3, 3), "cycles": n, "residual": s.last_residual}
+        j = SlabJacobi3D(parallel.DistContext(device=dev), planes, ny, nx, dtype=dt, check_every=100, accel="chebyshev")
+        setup(j, rhs)
+        j.run(200)  # warm
+        setup(j, rhs)
+        j.iteration = 0
+        sync()
+        t0 = time.perf_counter()
+        j.run(a.max_jacobi_iters, tol=a.tol)
+        sync()
+        solve.update({"jacobi_solve_ms": round((time.perf_counter() - t0) * 1e3, 3), "jacobi_iterations": j.iteration,
+                      "jacobi_residual": j.last_residual})
+        solve["jacobi_over_multigrid"] = round(solve["jacobi_solve_ms"] / solve["solve_ms"], 2)
+        solve["max_abs_difference"] = float((s.u - j.u).abs().max())
+
+    print(json.dumps({
+        "metric": "3-D Poisson multigrid V(2,2) cycle time on one MI355X",
+        "value": None if cycle_ms is None else round(cycle_ms, 4), "unit": "ms/cycle", "higher_is_better": False,
+        "grid": [planes + 2, ny, nx], "dtype": "fp32" if a.fp32 else "fp64", "levels": len(levels),
+        "coarsest": list(levels[-1]), "reps": a.reps, "tol": a.tol, "walk": ops.mg3_walk(),
+        "below_level2_share": None if share is None else round(share, 3),
+        "level0_kernels": kern, **solve}), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
