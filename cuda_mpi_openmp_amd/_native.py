@@ -142,6 +142,11 @@ _SIGNATURES = {
     "mpx_mg3_prolong_add_f64": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64, c_vp]),
     "mpx_mg3_prolong_add_f32": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64, c_vp]),
     "mpx_mg3_walk": (c_int, [_ip]),
+    # the coarse levels of a V-cycle in one kernel: (levels, n, nu1, nu2, coarse_sweeps, omega, stream)
+    "mpx_mg_tail_f64": (c_int, [c_vp, c_int, c_int, c_int, c_int, ctypes.c_double, c_vp]),
+    "mpx_mg_tail_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, ctypes.c_double, c_vp]),
+    "mpx_mg3_tail_f64": (c_int, [c_vp, c_int, c_int, c_int, c_int, ctypes.c_double, c_vp]),
+    "mpx_mg3_tail_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, ctypes.c_double, c_vp]),
     "mpx_cpu_jacobi3d_relax_f64": (ctypes.c_double, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_int,
                                                      ctypes.c_double]),
     "mpx_cpu_mg3_residual_f64": (ctypes.c_double, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64,
@@ -178,6 +183,20 @@ _SIGNATURES = {
     "mpx_sync_read": (c_int, [c_vp, c_int, ctypes.POINTER(ctypes.c_uint)]),
     "mpx_sync_clear": (c_int, [c_vp, c_i64]),
 }
+
+MG_TAIL_MAX_LEVELS = 16
+
+
+class MgLevel(ctypes.Structure):
+    """mpx_mg_level (capi.h): one level of a fused 2-D multigrid tail."""
+    _fields_ = [("u", c_vp), ("un", c_vp), ("b", c_vp), ("r", c_vp), ("h", c_int), ("w", c_int), ("pitch", c_int)]
+
+
+class Mg3Level(ctypes.Structure):
+    """mpx_mg3_level (capi.h): one level of a fused 3-D multigrid tail."""
+    _fields_ = [("u", c_vp), ("un", c_vp), ("b", c_vp), ("r", c_vp), ("d", c_int), ("h", c_int), ("w", c_int),
+                ("pitch", c_int), ("plane", c_i64)]
+
 
 # tuning-only entry points (kernel variants, copy probes, the exhaustive
 # fast-sqrt self-test): libmpx_tune.so, built from native/tune/ and loaded only

@@ -18,7 +18,9 @@ and the coarse grid keeps an interior. One V(nu1, nu2) cycle at level l:
 The coarsest level runs ``coarse_sweeps`` sweeps, or, with a single interior
 point, one undamped sweep (the exact solve up to rounding). Every operator has
 one defined rounding order, so a GPU fp64 cycle is bit-identical to the CPU
-cycle. All buffers are allocated in the constructor, with the row pitch rounded
+cycle. With ``tail_points`` the levels of at most that many points run in one
+kernel of one workgroup (``ops.mg_tail``), bit-identical to their launches.
+All buffers are allocated in the constructor, with the row pitch rounded
 up to 16 bytes so the odd widths take the vector kernels; ``cycle()``
 allocates nothing.
 """
@@ -30,7 +32,8 @@ from typing import Callable, List, Optional, Tuple
 
 import torch
 
-from .. import ops
+from .. import _native, ops
+from ..ops.multigrid import _tail_desc, _tail_launch
 
 
 class _Level:
@@ -63,10 +66,21 @@ class PoissonMultigrid:
     V-cycle and returns the fused max|s - u| of level 0's last post-smoothing
     sweep (``last_residual``, ``SlabJacobi.last_residual``'s meaning);
     ``solve(tol)`` cycles until it is at most ``tol``. ``cycles`` counts the
-    cycles run. float64 on CPU tensors, float64 / float32 on the GPU."""
+    cycles run. float64 on CPU tensors, float64 / float32 on the GPU.
+
+    ``tail_points``: the finest level k >= 1 with at most that many points
+    (H * W) and every level below it run as one kernel (``tail_level``: its
+    index, or None); 0: every level is launched; None: the measured default
+    on the GPU (``DEFAULT_TAIL_POINTS``), 0 on CPU tensors. The results do not
+    depend on it. ``launches_per_cycle``: the launches of one cycle, the fill
+    of a coarse u counted as one."""
+
+    # tail_points=None on the GPU: the threshold with the shortest measured cycle, per dtype (profiles/multigrid.md)
+    DEFAULT_TAIL_POINTS = {torch.float64: 4225, torch.float32: 16641}
 
     def __init__(self, rows: int, cols: int, dtype=torch.float64, device=None, nu1: int = 2, nu2: int = 2,
-                 omega: float = 0.8, coarse_sweeps: int = 50, max_levels: Optional[int] = None):
+                 omega: float = 0.8, coarse_sweeps: int = 50, max_levels: Optional[int] = None,
+                 tail_points: Optional[int] = None):
         if rows < 1 or cols < 3:
             raise ValueError("need at least 1 interior row and 3 columns")
         if nu1 < 0 or nu2 < 1:
@@ -78,6 +92,8 @@ class PoissonMultigrid:
             raise ValueError("omega must be finite and positive")
         if max_levels is not None and max_levels < 1:
             raise ValueError("max_levels must be at least 1")
+        if tail_points is not None and tail_points < 0:
+            raise ValueError("tail_points must be at least 0")
         self.device = torch.device("cpu" if device is None else device)
         if self.device.type != "cuda" and dtype != torch.float64:
             raise ValueError("the CPU model is float64")
@@ -92,6 +108,33 @@ class PoissonMultigrid:
         self.resid = torch.zeros(1, dtype=dtype, device=self.device)
         self.cycles = 0
         self.last_residual: Optional[float] = None
+        if tail_points is None:
+            tail_points = self.DEFAULT_TAIL_POINTS[dtype] if self.device.type == "cuda" else 0
+        self.tail_points = int(tail_points)
+        self.tail_level: Optional[int] = next(
+            (k for k in range(1, len(self.levels)) if math.prod(self.levels[k]) <= self.tail_points), None)
+        self._tail_sweeps: List[int] = []
+        self._tail_desc = None
+        if self.tail_level is not None:
+            tail = self._lv[self.tail_level:]
+            self._tail_sweeps = ops.tail_sweeps(len(tail), self.nu1, self.nu2, self.coarse_sweeps,
+                                                math.prod(self.levels[-1]) == 9)
+            if self.device.type == "cuda":
+                # validated once; _tail() only refreshes the u / un pointers (host memory only)
+                self._tail_desc = _tail_desc([(lv.u, lv.un, lv.b, lv.r) for lv in tail])
+
+    @property
+    def launches_per_cycle(self) -> int:
+        """Kernel launches of one cycle (the fill of a coarse u counts as one;
+        the zeroing of the residual word does not)."""
+        n = len(self.levels)
+        if n == 1:
+            return self.nu1 + self.nu2
+        launched = n - 1 if self.tail_level is None else self.tail_level
+        total = launched * (self.nu1 + self.nu2 + 4)
+        if self.tail_level is not None:
+            return total + 1
+        return total + (1 if math.prod(self.levels[-1]) == 9 else self.coarse_sweeps)
 
     @staticmethod
     def level_shapes(rows: int, cols: int, max_levels: Optional[int] = None) -> List[Tuple[int, int]]:
@@ -159,7 +202,26 @@ class PoissonMultigrid:
         ops.jacobi_relax(lv.u, lv.un, 1, lv.h - 1, omega, self.resid if track else None, rhs=lv.b)
         lv.u, lv.un = lv.un, lv.u
 
+    def _tail(self) -> None:
+        """Levels ``tail_level`` and below in one kernel; leaves the level
+        objects as their launches would (u and un swapped after an odd number
+        of sweeps)."""
+        tail = self._lv[self.tail_level:]
+        if self._tail_desc is None:
+            ops.mg_tail([(lv.u, lv.un, lv.b, lv.r) for lv in tail], self.nu1, self.nu2, self.coarse_sweeps, self.omega)
+        else:
+            for d, lv in zip(self._tail_desc, tail):
+                d.u, d.un = lv.u.data_ptr(), lv.un.data_ptr()
+            _tail_launch(self._tail_desc, self.dtype, self.nu1, self.nu2, self.coarse_sweeps, self.omega,
+                         _native.stream_of(tail[0].u))
+        for lv, n in zip(tail, self._tail_sweeps):
+            if n & 1:
+                lv.u, lv.un = lv.un, lv.u
+
     def _vcycle(self, k: int) -> None:
+        if k == self.tail_level:
+            self._tail()
+            return
         lv = self._lv[k]
         if k + 1 == len(self._lv) and k > 0:
             if lv.h == 3 and lv.w == 3:

@@ -5,8 +5,8 @@ from .classify import class_stats, classify_
 from .classify import plan as classify_plan
 from .edge import ConvLauncher, conv, conv_rows, roberts, roberts_rgb
 from .filters import Filter, get_filter, list_filters
-from .multigrid import jacobi_relax, mg_prolong_add_, mg_residual, mg_restrict
-from .multigrid3d import jacobi3d_relax, mg3_prolong_add_, mg3_residual, mg3_restrict, mg3_walk
+from .multigrid import jacobi_relax, mg_prolong_add_, mg_residual, mg_restrict, mg_tail, tail_sweeps
+from .multigrid3d import jacobi3d_relax, mg3_prolong_add_, mg3_residual, mg3_restrict, mg3_tail, mg3_walk
 from .sort import argsort, sort, sort_, sort_pairs_
 from .stencil import jacobi3d_sweep, jacobi3d_tile, jacobi_sweep
 from .vector import vsub
@@ -35,6 +35,9 @@ __all__ = [
     "mg3_restrict",
     "mg3_prolong_add_",
     "mg3_walk",
+    "mg_tail",
+    "mg3_tail",
+    "tail_sweeps",
     "argsort",
     "sort",
     "sort_",

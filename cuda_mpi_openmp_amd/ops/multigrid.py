@@ -175,3 +175,131 @@ def mg_prolong_add_(e: torch.Tensor, u: torch.Tensor) -> None:
         return
     if L.mpx_cpu_mg_prolong_add_f64(e.data_ptr(), u.data_ptr(), hc, wc, pe, pu) != 0:
         raise ValueError("mg_prolong_add_: bad arguments")
+
+
+# ---------------------------------------------------------------------------
+# the coarse levels of a V-cycle in one kernel
+# ---------------------------------------------------------------------------
+def tail_sweeps(n: int, nu1: int, nu2: int, coarse_sweeps: int, single_point_last: bool) -> list:
+    """Sweeps run by each of the ``n`` levels of a fused tail: nu1 + nu2, and
+    on the last level ``coarse_sweeps`` or 1 (a single interior point). A
+    level's iterate ends in ``un`` when its count is odd, in ``u`` otherwise."""
+    last = 1 if single_point_last else coarse_sweeps
+    return [nu1 + nu2] * (n - 1) + [last]
+
+
+def _tail_params(nu1, nu2, coarse_sweeps, omega):
+    nu1, nu2, coarse_sweeps, omega = int(nu1), int(nu2), int(coarse_sweeps), float(omega)
+    if nu1 < 0 or nu2 < 1:
+        raise ValueError("need nu1 >= 0 and nu2 >= 1")
+    if coarse_sweeps < 1:
+        raise ValueError("need coarse_sweeps >= 1")
+    if not (math.isfinite(omega) and omega > 0.0):
+        raise ValueError("omega must be finite and positive")
+    return nu1, nu2, coarse_sweeps, omega
+
+
+def _tail_levels(levels, what: str):
+    levels = [tuple(lv) for lv in levels]
+    if not 1 <= len(levels) <= _native.MG_TAIL_MAX_LEVELS:
+        raise ValueError(f"{what} takes 1 to {_native.MG_TAIL_MAX_LEVELS} levels")
+    if any(len(lv) != 4 for lv in levels):
+        raise ValueError(f"{what}: a level is (u, un, b, r_or_None)")
+    if any(lv[3] is None for lv in levels[:-1]):
+        raise ValueError(f"{what}: every level but the last needs r")
+    return levels
+
+
+def _tail_desc(levels):
+    """The validated mpx_mg_level array of ``levels``: u, un, b and r of a
+    level share one shape and one row pitch, and every level is the coarse
+    grid of the one before it."""
+    levels = _tail_levels(levels, "mg_tail")
+    desc = (_native.MgLevel * len(levels))()
+    for k, (u, un, b, r) in enumerate(levels):
+        pitch = _pitched(f"levels[{k}].u", u)
+        for name, t in (("un", un), ("b", b), ("r", r)):
+            if t is None:
+                continue
+            if _pitched(f"levels[{k}].{name}", t) != pitch or t.shape != u.shape:
+                raise ValueError(f"levels[{k}]: {name} must have u's shape and row pitch")
+            _same_kind("u", u, name, t)
+        if k:
+            _same_kind("levels[0].u", levels[0][0], f"levels[{k}].u", u)
+            _coarse_of(levels[k - 1][0], u, f"levels[{k - 1}].u", f"levels[{k}].u")
+        h, w = u.shape
+        if h < 3 or w < 3:
+            raise ValueError(f"levels[{k}]: need at least 3 rows and 3 columns")
+        desc[k] = _native.MgLevel(u.data_ptr(), un.data_ptr(), b.data_ptr(), None if r is None else r.data_ptr(), h, w,
+                                  pitch)
+    _check_dtype(levels[0][0], "mg_tail")
+    return desc
+
+
+def _tail_launch(desc, dtype, nu1, nu2, coarse_sweeps, omega, stream) -> None:
+    L = _native.lib()
+    fn = L.mpx_mg_tail_f64 if dtype == torch.float64 else L.mpx_mg_tail_f32
+    _native.check(fn(desc, len(desc), nu1, nu2, coarse_sweeps, omega, stream))
+
+
+def _tail_on_cpu(levels, nu1, nu2, coarse_sweeps, omega, single_point, relax, residual, restrict, prolong_add_) -> None:
+    """The fused tail's sequence with the launched operators, on the caller's
+    buffers: sweeps ping-pong between u and un, starting from u."""
+    cur = [[u, un] for u, un, _, _ in levels]
+
+    def sweep(k, om):
+        relax(cur[k][0], cur[k][1], om, levels[k][2])
+        cur[k].reverse()
+
+    n = len(levels)
+    for k in range(n - 1):
+        for _ in range(nu1):
+            sweep(k, omega)
+        residual(cur[k][0], levels[k][3], rhs=levels[k][2])
+        restrict(levels[k][3], levels[k + 1][2])
+        levels[k + 1][0].zero_()
+    if single_point(levels[-1][0]):
+        sweep(n - 1, 1.0)
+    else:
+        for _ in range(coarse_sweeps):
+            sweep(n - 1, omega)
+    for k in range(n - 2, -1, -1):
+        prolong_add_(cur[k + 1][0], cur[k][0])
+        for _ in range(nu2):
+            sweep(k, omega)
+
+
+def mg_tail(levels, nu1: int, nu2: int, coarse_sweeps: int, omega: float) -> None:
+    """The V-cycle from ``levels[0]`` down to the coarsest level and back up, as
+    ``PoissonMultigrid._vcycle`` runs it for a level k >= 1. ``levels``: a
+    sequence of ``(u, un, b, r_or_None)``, finest first, each the coarse grid
+    of the one before it; the four tensors of a level share one shape and one
+    row pitch; only the last level may go without ``r``. Per level but the
+    last: ``nu1`` damped sweeps with the level's ``b``, the residual into
+    ``r``, full weighting into the next level's ``b``, the next level's ``u``
+    <- 0 (its H x W elements), the next level, prolongation added in place,
+    ``nu2`` sweeps. The last level: ``coarse_sweeps`` sweeps, or one undamped
+    sweep when it is 3 x 3.
+
+    Where the results lie: sweeps ping-pong between a level's ``u`` and ``un``,
+    starting from ``u`` (for a level below ``levels[0]``, from the zeroed
+    ``u``), so a level's iterate ends in ``un`` if it ran an odd number of
+    sweeps (``tail_sweeps``), in ``u`` otherwise; the other of the two and
+    ``r`` are scratch. Rows 0 and H - 1 of ``un`` are never written: as for
+    ``jacobi_relax`` they are input, the level's boundary values (zeros below
+    ``levels[0]``). ``b`` of every level below ``levels[0]`` holds the
+    restricted residual.
+
+    GPU tensors: one launch of one workgroup on the current stream, nothing
+    allocated, no synchronisation; bit-identical to the launched operators.
+    CPU float64 tensors: the same sequence with the CPU operators."""
+    nu1, nu2, coarse_sweeps, omega = _tail_params(nu1, nu2, coarse_sweeps, omega)
+    desc = _tail_desc(levels)
+    levels = [tuple(lv) for lv in levels]
+    u0 = levels[0][0]
+    if u0.is_cuda:
+        _tail_launch(desc, u0.dtype, nu1, nu2, coarse_sweeps, omega, _native.stream_of(u0))
+        return
+    _tail_on_cpu(levels, nu1, nu2, coarse_sweeps, omega, lambda t: tuple(t.shape) == (3, 3),
+                 lambda u, un, om, b: jacobi_relax(u, un, 1, u.shape[0] - 1, om, rhs=b), mg_residual, mg_restrict,
+                 mg_prolong_add_)

@@ -24,7 +24,7 @@ from typing import Optional, Tuple
 import torch
 
 from .. import _native
-from .multigrid import _check_dtype, _resid_ptr, _same_kind
+from .multigrid import _check_dtype, _resid_ptr, _same_kind, _tail_levels, _tail_on_cpu, _tail_params
 
 
 def _pitched3(name: str, t: torch.Tensor) -> Tuple[int, int]:
@@ -176,3 +176,66 @@ def mg3_prolong_add_(e: torch.Tensor, u: torch.Tensor) -> None:
         return
     if L.mpx_cpu_mg3_prolong_add_f64(e.data_ptr(), u.data_ptr(), dc, hc, wc, pe, se, pu, su) != 0:
         raise ValueError("mg3_prolong_add_: bad arguments")
+
+
+# ---------------------------------------------------------------------------
+# the coarse levels of a V-cycle in one kernel
+# ---------------------------------------------------------------------------
+def _tail3_desc(levels):
+    """The validated mpx_mg3_level array of ``levels``: u, un, b and r of a
+    level share one shape, row pitch and plane stride, and every level is the
+    coarse grid of the one before it."""
+    levels = _tail_levels(levels, "mg3_tail")
+    desc = (_native.Mg3Level * len(levels))()
+    for k, (u, un, b, r) in enumerate(levels):
+        strides = _pitched3(f"levels[{k}].u", u)
+        for name, t in (("un", un), ("b", b), ("r", r)):
+            if t is None:
+                continue
+            if _pitched3(f"levels[{k}].{name}", t) != strides or t.shape != u.shape:
+                raise ValueError(f"levels[{k}]: {name} must have u's shape, row pitch and plane stride")
+            _same_kind("u", u, name, t)
+        if k:
+            _same_kind("levels[0].u", levels[0][0], f"levels[{k}].u", u)
+            _coarse3_of(levels[k - 1][0], u, f"levels[{k - 1}].u", f"levels[{k}].u")
+        d, h, w = u.shape
+        if min(d, h, w) < 3:
+            raise ValueError(f"levels[{k}]: need at least 3 planes, 3 rows and 3 columns")
+        desc[k] = _native.Mg3Level(u.data_ptr(), un.data_ptr(), b.data_ptr(), None if r is None else r.data_ptr(), d, h,
+                                   w, strides[0], strides[1])
+    _check_dtype(levels[0][0], "mg3_tail")
+    return desc
+
+
+def _tail3_launch(desc, dtype, nu1, nu2, coarse_sweeps, omega, stream) -> None:
+    L = _native.lib()
+    fn = L.mpx_mg3_tail_f64 if dtype == torch.float64 else L.mpx_mg3_tail_f32
+    _native.check(fn(desc, len(desc), nu1, nu2, coarse_sweeps, omega, stream))
+
+
+def mg3_tail(levels, nu1: int, nu2: int, coarse_sweeps: int, omega: float) -> None:
+    """``mg_tail`` for the 3-D solver: the V-cycle from ``levels[0]`` down and
+    back up as ``PoissonMultigrid3D._vcycle`` runs it for a level k >= 1, with
+    ``jacobi3d_relax``, ``mg3_residual``, ``mg3_restrict`` and
+    ``mg3_prolong_add_``; the last level runs one undamped sweep when it is
+    3 x 3 x 3. ``levels``: ``(u, un, b, r_or_None)`` per level, finest first,
+    the four tensors of a level sharing one shape, row pitch and plane stride.
+
+    Where the results lie: as ``mg_tail`` — in ``un`` for a level that ran an
+    odd number of sweeps (``tail_sweeps``), in ``u`` otherwise, counted from
+    the zeroed ``u`` below ``levels[0]``; planes 0 and D - 1 and rows 0 and
+    H - 1 of ``un`` are never written: they are input, the boundary values.
+
+    GPU tensors: one launch of one workgroup on the current stream, nothing
+    allocated, no synchronisation; bit-identical to the launched operators.
+    CPU float64 tensors: the same sequence with the CPU operators."""
+    nu1, nu2, coarse_sweeps, omega = _tail_params(nu1, nu2, coarse_sweeps, omega)
+    desc = _tail3_desc(levels)
+    levels = [tuple(lv) for lv in levels]
+    u0 = levels[0][0]
+    if u0.is_cuda:
+        _tail3_launch(desc, u0.dtype, nu1, nu2, coarse_sweeps, omega, _native.stream_of(u0))
+        return
+    _tail_on_cpu(levels, nu1, nu2, coarse_sweeps, omega, lambda t: tuple(t.shape) == (3, 3, 3),
+                 lambda u, un, om, b: jacobi3d_relax(u, un, 1, u.shape[0] - 1, om, rhs=b), mg3_residual, mg3_restrict,
+                 mg3_prolong_add_)

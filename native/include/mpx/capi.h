@@ -499,6 +499,46 @@ int mpx_mg3_prolong_add_f32(const float *e, float *u, int dc, int hc, int wc, in
  * the transfers). out: 5 ints. */
 int mpx_mg3_walk(int *out);
 
+/* The coarse levels of a V-cycle in one kernel (native/src/kernels/mg_tail.hip):
+ * one workgroup runs, from lv[0] down to lv[n - 1] and back up, what the launched
+ * cycle runs for a level k >= 1. For every level but the last: nu1 damped sweeps
+ * (mpx_jacobi_relax / mpx_jacobi3d_relax over all interior rows / planes, with
+ * the level's b), the residual into r, full weighting of r into the next level's
+ * b, the next level's u <- 0 on its H x W (D x H x W) elements, the next level,
+ * prolongation added in place, nu2 damped sweeps. The last level: coarse_sweeps
+ * damped sweeps, or one sweep with omega = 1 when it is 3 x 3 (3 x 3 x 3). Every
+ * point's expression is that of the launched operator above, operation for
+ * operation, so the result is bit-identical to the launches.
+ *
+ * Sweeps ping-pong between a level's u and un, starting from u: afterwards a
+ * level's iterate lies in un when the level ran an odd number of sweeps
+ * (nu1 + nu2; the last level coarse_sweeps or 1), in u otherwise; the other of
+ * the two and r are scratch. Rows 0 and H - 1 (3-D: planes 0 and D - 1 too) of
+ * un are never written and are read by every second sweep: as for the launched
+ * sweeps they are input and hold the boundary values of the level (lv[0]: those
+ * of its u; below lv[0]: zeros). u, un, b and r of a level share its
+ * pitch (and plane stride); padding is never read for a result and never
+ * written; r of the last level may be NULL. One launch of one workgroup on
+ * `stream`; no allocation, no synchronisation, no residual maximum.
+ * MPX_ERR_ARG, nothing written: null pointers, n < 1 or n > 16, a level that is
+ * not the coarse grid of the one before it (H = 2 Hc - 1, ...), a dimension
+ * below 3, pitch < w, plane < h * pitch, nu1 < 0, nu2 < 1, coarse_sweeps < 1, an
+ * omega that is not finite and positive before and after its rounding to T. */
+#define MPX_MG_TAIL_MAX_LEVELS 16
+typedef struct mpx_mg_level {
+    void *u, *un, *b, *r;
+    int h, w, pitch;
+} mpx_mg_level;
+typedef struct mpx_mg3_level {
+    void *u, *un, *b, *r;
+    int d, h, w, pitch;
+    int64_t plane;
+} mpx_mg3_level;
+int mpx_mg_tail_f64(const mpx_mg_level *lv, int n, int nu1, int nu2, int coarse_sweeps, double omega, void *stream);
+int mpx_mg_tail_f32(const mpx_mg_level *lv, int n, int nu1, int nu2, int coarse_sweeps, double omega, void *stream);
+int mpx_mg3_tail_f64(const mpx_mg3_level *lv, int n, int nu1, int nu2, int coarse_sweeps, double omega, void *stream);
+int mpx_mg3_tail_f32(const mpx_mg3_level *lv, int n, int nu1, int nu2, int coarse_sweeps, double omega, void *stream);
+
 /* ---------------- lab5: ascending sort (no reference program) ---------------- */
 /* In place on the device; dtype is an mpx_sort_dtype. int32/float32: LSD radix sort
  * (onesweep, 8-bit digits) on order-preserving uint32 keys, bitonic network for

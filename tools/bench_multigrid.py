@@ -6,6 +6,7 @@ solve of the same problem in the same session.
 
   python tools/bench_multigrid.py [--rows 2047] [--cols 2049] [--fp32]
                                   [--tol 1e-8] [--reps 20] [--no-solve]
+                                  [--tail-points N] [--tail-table]
 
 Per-kernel times: device events around single launches, median over --reps
 launches that rotate through buffer sets larger than the 256 MiB Infinity
@@ -15,6 +16,11 @@ prolong-add 2.25. ``rhs_sweep_even`` is ops.jacobi_sweep(rhs=) on the
 (rows + 2, cols - 1) grid, whose even width takes the wave-strip kernel: the
 gap to ``relax`` is what the odd width costs. ``below_level2_share`` is the
 time of the sub-cycle from level 2 down over the whole cycle (launch-bound).
+
+``--tail-points N``: the levels of at most N points run as one kernel (0: every
+level launched; default: the model's measured threshold); the JSON line carries
+``tail_points``, ``tail_level`` and ``launches_per_cycle``. ``--tail-table``: per
+level, the sub-cycle from that level down, launched and fused (``tail_table``).
 
 Prints one JSON line.
 """
@@ -92,6 +98,41 @@ def kernel_times(rows, cols, dt, reps, dev):
     return res
 
 
+def tail_table(rows, cols, dt, reps, max_points, dev):
+    """Per level k >= 1 of at most ``max_points`` points: the median time of the
+    sub-cycle from level k down, launched (``tail_points=0``) and as one kernel
+    (the tail starting at k), each between two device synchronisations."""
+    def sub_cycle_us(m, k):
+        ts = []
+        for i in range(reps + 3):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            m._vcycle(k)
+            torch.cuda.synchronize(dev)
+            if i >= 3:
+                ts.append(time.perf_counter() - t0)
+        return statistics.median(ts) * 1e6
+
+    launched = PoissonMultigrid(rows, cols, dtype=dt, device=dev, tail_points=0)
+    rows_out = []
+    for k in range(1, len(launched.levels)):
+        points = 1
+        for n in launched.levels[k]:
+            points *= n
+        if points > max_points:
+            continue
+        fused = PoissonMultigrid(rows, cols, dtype=dt, device=dev, tail_points=points)
+        assert fused.tail_level == k
+        for m in (launched, fused):
+            setup(m, rows, cols)
+            m.cycle()
+        a, b = sub_cycle_us(launched, k), sub_cycle_us(fused, k)
+        rows_out.append({"level": k, "shape": list(launched.levels[k]), "points": points, "launched_us": round(a, 1),
+                         "fused_us": round(b, 1), "launches": launched.launches_per_cycle - fused.launches_per_cycle + 1})
+        del fused
+    return rows_out
+
+
 def main() -> int:
     p = argparse.ArgumentParser()
     p.add_argument("--rows", type=int, default=2047)
@@ -101,6 +142,11 @@ def main() -> int:
     p.add_argument("--reps", type=int, default=20)
     p.add_argument("--no-solve", action="store_true", help="skip the solves (multigrid and Chebyshev Jacobi)")
     p.add_argument("--no-kernels", action="store_true", help="skip the per-kernel times")
+    p.add_argument("--tail-points", type=int, default=None,
+                   help="levels of at most this many points run as one kernel (0: none; default: the model's)")
+    p.add_argument("--tail-table", action="store_true",
+                   help="time the sub-cycle from every level of at most --tail-table-max points down, launched and fused")
+    p.add_argument("--tail-table-max", type=int, default=263169)
     p.add_argument("--max-jacobi-iters", type=int, default=200000)
     a = p.parse_args()
     if not torch.cuda.is_available():
@@ -114,7 +160,7 @@ def main() -> int:
     kern = None if a.no_kernels else kernel_times(rows, cols, dt, a.reps, dev)
 
     # one V-cycle: host clock around cycle() (it ends in the residual read)
-    mg = PoissonMultigrid(rows, cols, dtype=dt, device=dev)
+    mg = PoissonMultigrid(rows, cols, dtype=dt, device=dev, tail_points=a.tail_points)
     setup(mg, rows, cols)
     for _ in range(3):
         mg.cycle()
@@ -126,7 +172,7 @@ def main() -> int:
         ts.append(time.perf_counter() - t0)
     cycle_ms = statistics.median(ts) * 1e3
     share = None
-    if len(mg.levels) > 2:
+    if len(mg.levels) > 2 and (mg.tail_level is None or mg.tail_level >= 2):
         ts = []
         for _ in range(a.reps):
             sync()
@@ -136,9 +182,13 @@ def main() -> int:
             ts.append(time.perf_counter() - t0)
         share = statistics.median(ts) * 1e3 / cycle_ms
 
+    plan = {"tail_points": mg.tail_points, "tail_level": mg.tail_level, "launches_per_cycle": mg.launches_per_cycle}
+
+    table = tail_table(rows, cols, dt, a.reps, a.tail_table_max, dev) if a.tail_table else None
+
     solve = {}
     if not a.no_solve:
-        s = PoissonMultigrid(rows, cols, dtype=dt, device=dev)
+        s = PoissonMultigrid(rows, cols, dtype=dt, device=dev, tail_points=a.tail_points)
         setup(s, rows, cols)
         sync()
         t0 = time.perf_counter()
@@ -165,7 +215,7 @@ def main() -> int:
         "grid": [rows + 2, cols], "dtype": "fp32" if a.fp32 else "fp64", "levels": len(mg.levels),
         "coarsest": list(mg.levels[-1]), "reps": a.reps, "tol": a.tol,
         "below_level2_share": None if share is None else round(share, 3),
-        "level0_kernels": kern, **solve}), flush=True)
+        **plan, "tail_table": table, "level0_kernels": kern, **solve}), flush=True)
     return 0
 
 
