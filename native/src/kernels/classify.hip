@@ -946,6 +946,8 @@ __global__ __launch_bounds__(256) void classify_mfma8s_kernel(uint32_t *__restri
         v[vi] = make_uint4(o[0], o[1], o[2], o[3]);
     };
     uint4 qn = i < nvec ? v[i] : uint4{};
+    // a per-lane loop is fine here (unlike classify_mfma16_kernel's): lanes
+    // past the end leave stale integer features, and 0 x stale is 0 in int8
     for (; i < nvec; i += stride) {
         const uint4 q = qn;
         if (i + stride < nvec) qn = v[i + stride];
@@ -1251,7 +1253,14 @@ __global__ __launch_bounds__(256) void classify_mfma16_kernel(uint32_t *__restri
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint4 qn = i < nvec ? v[i] : uint4{};
-    for (; i < nvec; i += stride) {
+    // A wave walks the loop with all of its lanes (i - lane is the wave's first
+    // vector): the MFMA reads the B fragments of all 64 lanes, and although a
+    // lane's rows carry zero weights for the other half's k-block, 0 x a stale
+    // f16 NaN / Inf pattern in a lane that left the loop is NaN, which made
+    // every pixel of a partial last wave undecided (exact, but through the
+    // fallback). Lanes past the end rank a finite pixel and store nothing.
+    for (; i - lane < nvec; i += stride) {
+        const bool in = i < nvec;
         const uint4 q = qn;
         if (i + stride < nvec) qn = v[i + stride];
         const uint32_t px[4] = {q.x, q.y, q.z, q.w};
@@ -1259,7 +1268,7 @@ __global__ __launch_bounds__(256) void classify_mfma16_kernel(uint32_t *__restri
         bool u[4];
 #pragma unroll
         for (int m = 0; m < 4; ++m) o[m] = mfma16_pixel<NSET, NR>(px[m], L, T2, u[m]);
-        if (__builtin_expect(u[0] | u[1] | u[2] | u[3], 0)) {
+        if (__builtin_expect(in & (u[0] | u[1] | u[2] | u[3]), 0)) {
             const uint32_t mask = (uint32_t)u[0] | ((uint32_t)u[1] << 1) | ((uint32_t)u[2] << 2) | ((uint32_t)u[3] << 3);
             const uint32_t slot = atomicAdd(&s_namb[w], 1u);
             if (slot < (uint32_t)kAmb8sCapW) {
@@ -1270,7 +1279,7 @@ __global__ __launch_bounds__(256) void classify_mfma16_kernel(uint32_t *__restri
                     if ((mask >> m) & 1u) o[m] = classify_direct(px[m], nc, cp);
             }
         }
-        v[i] = make_uint4(o[0], o[1], o[2], o[3]);
+        if (in) v[i] = make_uint4(o[0], o[1], o[2], o[3]);
     }
     __builtin_amdgcn_wave_barrier();
     const uint32_t nd = min(s_namb[w], (uint32_t)kAmb8sCapW);

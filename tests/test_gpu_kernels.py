@@ -390,7 +390,7 @@ def test_classify_near_ties_fall_back_exactly(gpu):
     mu, inv = ops.class_stats(img, [pts, pts, pts[:-1]])
     cpu = img.clone()
     ops.classify_(cpu, mu, inv)
-    for path in ("fast", "mfma", "mfma64", "mfma8"):
+    for path in ("fast", "mfma", "mfma64", "mfma8", "mfma16", "auto"):
         d = img.to(gpu)
         ops.classify_(d, mu, inv, path=path)
         assert torch.equal(d.cpu(), cpu), path
