@@ -117,6 +117,9 @@ _SIGNATURES = {
     "mpx_cpu_mg_residual_f64": (ctypes.c_double, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int]),
     "mpx_cpu_mg_restrict_f64": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int]),
     "mpx_cpu_mg_prolong_add_f64": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int]),
+    "mpx_mg_prolong_cubic_f64": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
+    "mpx_mg_prolong_cubic_f32": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
+    "mpx_cpu_mg_prolong_cubic_f64": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int]),
     # 3-D sweeps: (u, b or NULL, un, nx, ny, k0, k1, [omega,] resid, stream)
     "mpx_jacobi3d_f64": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "mpx_jacobi3d_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),

@@ -5,7 +5,8 @@ from .classify import class_stats, classify_
 from .classify import plan as classify_plan
 from .edge import ConvLauncher, conv, conv_rows, roberts, roberts_rgb
 from .filters import Filter, get_filter, list_filters
-from .multigrid import jacobi_relax, mg_prolong_add_, mg_residual, mg_restrict, mg_tail, tail_sweeps
+from .multigrid import (jacobi_relax, mg_prolong_add_, mg_prolong_cubic, mg_residual, mg_restrict, mg_tail,
+                        tail_sweeps)
 from .multigrid3d import jacobi3d_relax, mg3_prolong_add_, mg3_residual, mg3_restrict, mg3_tail, mg3_walk
 from .sort import argsort, sort, sort_, sort_pairs_
 from .stencil import jacobi3d_sweep, jacobi3d_tile, jacobi_sweep
@@ -30,6 +31,7 @@ __all__ = [
     "mg_residual",
     "mg_restrict",
     "mg_prolong_add_",
+    "mg_prolong_cubic",
     "jacobi3d_relax",
     "mg3_residual",
     "mg3_restrict",

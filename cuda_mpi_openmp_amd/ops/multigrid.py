@@ -177,6 +177,36 @@ def mg_prolong_add_(e: torch.Tensor, u: torch.Tensor) -> None:
         raise ValueError("mg_prolong_add_: bad arguments")
 
 
+def mg_prolong_cubic(c: torch.Tensor, u: torch.Tensor) -> None:
+    """Cubic interpolation of the coarse ``c`` (Hc, Wc) written over the fine
+    interior of ``u`` (2 Hc - 1, 2 Wc - 1): the interpolant of full multigrid,
+    which carries a solution (with its Dirichlet values in c's boundary) where
+    ``mg_prolong_add_`` carries a correction. u's boundary is not written; c's
+    boundary is read; Hc, Wc >= 3.
+
+    The 1-D rule takes c[0..n-1] to 2n - 1 values: the even ones copy c, the
+    midpoint between K and K + 1 is m = (a + (a - o) * 0.125) * 0.5 with
+    a = c[K] + c[K+1], o = c[K-1] + c[K+2] (the weights (-1, 9, 9, -1) / 16).
+    c[-1] and c[n] are ghosts extrapolated from the same values: for n >= 4
+    c[-1] = ((c[0] + c[2]) * 4 - c[3]) - c[1] * 6 (which makes the end midpoint
+    the one-sided cubic (5, 15, -5, 1) / 16), for n = 3
+    c[-1] = (c[0] - c[1]) * 3 + c[2] (the parabola (3, 6, -1) / 8), and c[n]
+    is the mirror image. The 2-D rule applies the 1-D rule along every coarse
+    row and then down the columns of the Hc interpolated rows, whose ghost
+    rows are formed element by element."""
+    pu, pc, hc, wc = _coarse_of(u, c, "u", "c")
+    if hc < 3 or wc < 3:
+        raise ValueError("mg_prolong_cubic needs a coarse grid of at least 3 x 3")
+    _check_dtype(u, "mg_prolong_cubic")
+    L = _native.lib()
+    if u.is_cuda:
+        fn = L.mpx_mg_prolong_cubic_f64 if u.dtype == torch.float64 else L.mpx_mg_prolong_cubic_f32
+        _native.check(fn(c.data_ptr(), u.data_ptr(), hc, wc, pc, pu, _native.stream_of(u)))
+        return
+    if L.mpx_cpu_mg_prolong_cubic_f64(c.data_ptr(), u.data_ptr(), hc, wc, pc, pu) != 0:
+        raise ValueError("mg_prolong_cubic: bad arguments")
+
+
 # ---------------------------------------------------------------------------
 # the coarse levels of a V-cycle in one kernel
 # ---------------------------------------------------------------------------

@@ -237,6 +237,41 @@ def mg_prolong_add(e: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _cubic_rows(c: torch.Tensor) -> torch.Tensor:
+    """``mg_prolong_cubic``'s 1-D rule along the last dimension: (..., n) to
+    (..., 2n - 1), every operation rounded in c's dtype."""
+    n = c.shape[-1]
+    if n >= 4:
+        gl = ((c[..., 0] + c[..., 2]) * 4 - c[..., 3]) - c[..., 1] * 6
+        gr = ((c[..., -1] + c[..., -3]) * 4 - c[..., -4]) - c[..., -2] * 6
+    else:
+        gl = (c[..., 0] - c[..., 1]) * 3 + c[..., 2]
+        gr = (c[..., 2] - c[..., 1]) * 3 + c[..., 0]
+    x = torch.cat([gl.unsqueeze(-1), c, gr.unsqueeze(-1)], dim=-1)
+    a = x[..., 1:-2] + x[..., 2:-1]
+    o = x[..., :-3] + x[..., 3:]
+    out = torch.empty(c.shape[:-1] + (2 * n - 1,), dtype=c.dtype)
+    out[..., 0::2] = c
+    out[..., 1::2] = (a + (a - o) * 0.125) * 0.5
+    return out
+
+
+def mg_prolong_cubic(c: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+    """u with its interior replaced by the cubic interpolation of the coarse c,
+    in u's dtype and the kernels' order: the 1-D rule of ``ops.mg_prolong_cubic``
+    along every coarse row, then down the columns of the interpolated rows;
+    u's boundary is returned unchanged."""
+    u = u.cpu()
+    c = c.cpu().to(u.dtype)
+    hc, wc = c.shape
+    if hc < 3 or wc < 3 or u.shape != (2 * hc - 1, 2 * wc - 1):
+        raise ValueError("u must be (2 Hc - 1, 2 Wc - 1) with Hc, Wc >= 3")
+    full = _cubic_rows(_cubic_rows(c).t()).t()
+    out = u.clone()
+    out[1:-1, 1:-1] = full[1:-1, 1:-1]
+    return out
+
+
 def mg3_residual(u: torch.Tensor, rhs: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
     """3-D multigrid residual in u's own dtype, in the kernels' association:
     r = ((((zm + zp) + (ym + yp)) + (xm + xp)) [+ b]) - 6 c at the interior

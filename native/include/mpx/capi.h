@@ -388,7 +388,23 @@ int mpx_jacobi_relax_f32(const float *u, const float *b, float *un, int cols, in
  *     u[2I+1][2J]   += (e[I][J] + e[I+1][J]) * 0.5
  *     u[2I][2J+1]   += (e[I][J] + e[I][J+1]) * 0.5
  *     u[2I+1][2J+1] += ((e[I][J] + e[I+1][J]) + (e[I][J+1] + e[I+1][J+1])) * 0.25
- *   e's boundary is read; u's boundary is not written. hc, wc >= 2. */
+ *   e's boundary is read; u's boundary is not written. hc, wc >= 2.
+ * prolong_cubic (cubic interpolation of the coarse c written over u's interior;
+ *   the interpolant of full multigrid). The 1-D rule takes n >= 3 values
+ *   c[0..n-1] to 2n - 1 values: the even ones copy c, and the midpoint between
+ *   K and K + 1 is, with a = c[K] + c[K+1] and o = c[K-1] + c[K+2],
+ *     m = (a + (a - o) * 0.125) * 0.5
+ *   (the weights (-1, 9, 9, -1) / 16). c[-1] and c[n] are ghosts extrapolated
+ *   from the same values:
+ *     n >= 4: c[-1] = ((c[0] + c[2]) * 4 - c[3]) - c[1] * 6
+ *             c[n]  = ((c[n-1] + c[n-3]) * 4 - c[n-4]) - c[n-2] * 6
+ *     n == 3: c[-1] = (c[0] - c[1]) * 3 + c[2],  c[3] = (c[2] - c[1]) * 3 + c[0]
+ *   (with the midpoint rule: the one-sided cubic (5, 15, -5, 1) / 16 and the
+ *   parabola (3, 6, -1) / 8). The 2-D rule applies the 1-D rule along every
+ *   coarse row, which gives hc rows of width W, and then down the columns of
+ *   those rows; the ghost rows are formed element by element from the
+ *   interpolated rows. c's boundary is read (the coarse Dirichlet values); only
+ *   u's interior is written. hc, wc >= 3. */
 int mpx_mg_residual_f64(const double *u, const double *b, double *r, int rows, int cols, int pitch_u, int pitch_b,
                         int pitch_r, double *resid, void *stream);
 int mpx_mg_residual_f32(const float *u, const float *b, float *r, int rows, int cols, int pitch_u, int pitch_b,
@@ -397,6 +413,8 @@ int mpx_mg_restrict_f64(const double *r, double *bc, int hc, int wc, int pitch_r
 int mpx_mg_restrict_f32(const float *r, float *bc, int hc, int wc, int pitch_r, int pitch_bc, void *stream);
 int mpx_mg_prolong_add_f64(const double *e, double *u, int hc, int wc, int pitch_e, int pitch_u, void *stream);
 int mpx_mg_prolong_add_f32(const float *e, float *u, int hc, int wc, int pitch_e, int pitch_u, void *stream);
+int mpx_mg_prolong_cubic_f64(const double *c, double *u, int hc, int wc, int pitch_c, int pitch_u, void *stream);
+int mpx_mg_prolong_cubic_f32(const float *c, float *u, int hc, int wc, int pitch_c, int pitch_u, void *stream);
 
 /* 3-D sweeps (the 7-point Laplace / Poisson stencil). u, un and the optional b
  * are contiguous (planes + 2) x ny x nx buffers, x fastest; planes 0 and
@@ -605,6 +623,7 @@ double mpx_cpu_mg_residual_f64(const double *u, const double *b, double *r, int 
                                int pitch_b, int pitch_r);
 int mpx_cpu_mg_restrict_f64(const double *r, double *bc, int hc, int wc, int pitch_r, int pitch_bc);
 int mpx_cpu_mg_prolong_add_f64(const double *e, double *u, int hc, int wc, int pitch_e, int pitch_u);
+int mpx_cpu_mg_prolong_cubic_f64(const double *c, double *u, int hc, int wc, int pitch_c, int pitch_u);
 /* the 3-D sweeps of mpx_jacobi3d_f64 / mpx_jacobi3d_accel_f64 (b may be NULL);
  * both return the residual, or NaN, with nothing written, on a null u / un,
  * bad geometry or a bad omega */

@@ -564,6 +564,69 @@ int mpx_cpu_mg_prolong_add_f64(const double *e, double *u, int hc, int wc, int p
     return 0;
 }
 
+/* prolong_cubic (capi.h): the midpoint of four values, the ghost before c0, and
+ * element j of a row of n values interpolated to 2n - 1 */
+static inline double cubic_mid(double cm, double c0, double c1, double c2) {
+    const double a = c0 + c1;
+    const double o = cm + c2;
+    const double d = a - o;
+    const double t = a + d * 0.125;
+    return t * 0.5;
+}
+
+static inline double cubic_ghost(int n, double c0, double c1, double c2, double c3) {
+    if (n >= 4) {
+        const double s = c0 + c2;
+        const double q = s * 4.0 - c3;
+        return q - c1 * 6.0;
+    }
+    const double d = c0 - c1;
+    return d * 3.0 + c2;
+}
+
+static inline double cubic_row(const double *c, int n, int j) {
+    const int K = j / 2;
+    if (!(j & 1)) return c[K];
+    const double cm = K >= 1 ? c[K - 1] : cubic_ghost(n, c[0], c[1], c[2], c[n >= 4 ? 3 : 2]);
+    const double cp = K + 2 < n ? c[K + 2] : cubic_ghost(n, c[n - 1], c[n - 2], c[n - 3], c[n >= 4 ? n - 4 : 0]);
+    return cubic_mid(cm, c[K], c[K + 1], cp);
+}
+
+int mpx_cpu_mg_prolong_cubic_f64(const double *c, double *u, int hc, int wc, int pitch_c, int pitch_u) {
+    int i;
+    if (!c || !u || hc < 3 || wc < 3 || hc >= (1 << 29) || wc >= (1 << 29) || pitch_c < wc || pitch_u < 2 * wc - 1)
+        return -1;
+    const int h = 2 * hc - 1, w = 2 * wc - 1;
+#pragma omp parallel for schedule(static)
+    for (i = 1; i < h - 1; ++i) {
+        const int K = i / 2;
+        double *o = u + (int64_t)i * pitch_u;
+        for (int j = 1; j < w - 1; ++j) {
+            if (!(i & 1)) {
+                o[j] = cubic_row(c + (int64_t)K * pitch_c, wc, j);
+                continue;
+            }
+            /* column j of the interpolated rows K - 1 .. K + 2, the ghost rows from the first / last four */
+            double v[4];
+            for (int q = 0; q < 4; ++q) {
+                const int I = K - 1 + q;
+                if (I >= 0 && I < hc) {
+                    v[q] = cubic_row(c + (int64_t)I * pitch_c, wc, j);
+                } else {
+                    double g[4];
+                    for (int t = 0; t < 4; ++t) {
+                        const int R = t < 3 || hc >= 4 ? t : 0; /* hc == 3: the fourth is not used */
+                        g[t] = cubic_row(c + (int64_t)(I < 0 ? R : hc - 1 - R) * pitch_c, wc, j);
+                    }
+                    v[q] = cubic_ghost(hc, g[0], g[1], g[2], g[3]);
+                }
+            }
+            o[j] = cubic_mid(v[0], v[1], v[2], v[3]);
+        }
+    }
+    return 0;
+}
+
 /* 3-D sweep over planes [k0, k1) of a (planes + 2, ny, nx) buffer, x fastest:
  * s = ((((zm + zp) + (ym + yp)) + (xm + xp)) [+ b]) * (1/6), every operation
  * rounded (-ffp-contract=off), in the GPU kernels' association. Boundary rows

@@ -7,8 +7,8 @@
 // coarse point (I, J) on fine point (2I, 2J). Every tensor has its own row
 // pitch (elements); padding is never read and never written.
 //
-// MI355X design: all three kernels are HBM-bound (3 / 1.25 / 2.25 words per
-// fine point), so
+// MI355X design: the kernels are HBM-bound (residual 3, restrict 1.25,
+// prolong-add 2.25, cubic prolong 1.25 words per fine point), so
 //   * a lane owns one 16-B vector of the narrower grid per row (residual: of
 //     u; restrict and prolong: of the coarse grid, and with it the two fine
 //     vectors below it) and walks a block of rows down, so every input row is
@@ -17,13 +17,14 @@
 //     mg_rows_per_lane, profiles/multigrid.md);
 //   * the even/odd column interleave of the transfers happens inside the lane
 //     (coarse vector k <-> fine elements 2k, 2k+1 of the lane's vector pair);
-//     the one element a lane needs from its neighbour comes through a DPP wave
-//     shift, and only lanes 0 / 63 of a wave load it themselves — no strided
-//     global access;
+//     the one element a lane needs from its neighbour (the cubic prolongation:
+//     one from the left, two from the right) comes through a DPP wave shift,
+//     and only lanes 0 / 63 of a wave load it themselves — no strided global
+//     access;
 //   * the VEC = false form (one element per lane, scalar loads) serves bases
 //     and pitches that are not 16-byte multiples, as jacobi_kernel<T, false>;
 //   * every + - * is one rounded operation (-ffp-contract=off), in the order
-//     written in capi.h; the factors 4, 0.5 and 0.25 are exact.
+//     written in capi.h; the factors 4, 0.5, 0.25 and 0.125 are exact.
 #include "mg_lane.hpp"
 
 namespace mpx {
@@ -31,6 +32,9 @@ namespace {
 
 constexpr int kMgRows = 16;       // rows of the residual walked per lane
 constexpr int kMgCoarseRows = 8;  // coarse rows walked per lane by the transfers
+// and by the cubic prolongation: 8193^2 measured fastest at 2 in both dtypes (fp64
+// 223 us against 262 / 234 / 253 / 270 at 1 / 4 / 8 / 16: profiles/multigrid.md)
+constexpr int kMgCubicRows = 2;
 // a launch halves its rows per lane until it has this many waves (or one row):
 // the coarser levels have too few columns to fill the device with long walks
 constexpr int kMgMinWaves = 8192;
@@ -205,6 +209,146 @@ __global__ __launch_bounds__(256) void mg_prolong_kernel(const T *__restrict__ e
     }
 }
 
+// the midpoint of the cubic through four equidistant values (weights
+// (-1, 9, 9, -1) / 16, the scale factors exact) and the value one step before
+// c0 on the cubic through c0..c3 (CUBIC) or the parabola through c0..c2
+template <typename T>
+__device__ __forceinline__ T cubic_mid(T cm, T c0, T c1, T c2) {
+    const T a = c0 + c1;
+    const T o = cm + c2;
+    const T d = a - o;
+    const T t = a + d * (T)0.125;
+    return t * (T)0.5;
+}
+
+template <typename T>
+__device__ __forceinline__ T cubic_ghost(bool cubic, T c0, T c1, T c2, T c3) {
+    const T s = c0 + c2;
+    const T q = s * (T)4 - c3;
+    const T g4 = q - c1 * (T)6;
+    const T d = c0 - c1;
+    const T g3 = d * (T)3 + c2;
+    return cubic ? g4 : g3;
+}
+
+// cubic interpolation of the coarse c written to the fine interior of u (the
+// FMG interpolant). A lane owns the coarse columns [J0, J0 + NV) and the fine
+// columns [2 J0, 2 J0 + 2 NV) below them. A coarse row is interpolated along
+// the row as it is fetched (ev: the fine columns 2J, od: 2J + 1); the lane
+// lacks c[J0 - 1], c[J0 + NV] and c[J0 + NV + 1], which come from its
+// neighbours by wave shifts. A block walks R coarse rows: it fetches the rows
+// I0 - 1 .. I0 + R + 1 in one group of loads, each once, and keeps them
+// interpolated in registers; fine row 2I is row I, fine row 2I + 1 the cubic
+// midpoint of the rows I - 1 .. I + 2. The ghost columns c[-1] and c[wc] are
+// computed by every lane from the ends of the row (uniform addresses) and
+// selected by column; the ghost rows -1 and hc are formed from the
+// interpolated rows under block-uniform conditions
+template <typename T, bool VEC, int R>
+__global__ __launch_bounds__(256) void mg_prolong_cubic_kernel(const T *__restrict__ c, T *__restrict__ u, int hc,
+                                                               int wc, int pc, int pu) {
+    constexpr int NV = VEC ? JVec<T>::n : 1;
+    constexpr int M = R + 3;
+    const int J0 = NV * (blockIdx.x * blockDim.x + threadIdx.x);
+    const int f0 = 2 * J0;
+    const int w = 2 * wc - 1;
+    const int I0 = blockIdx.y * R;
+    const bool wcubic = wc >= 4, hcubic = hc >= 4;
+    // slot q holds row I0 - 1 + q. Where that is a ghost row the slot fetches the
+    // fourth row the ghost is made of: row 3 for row -1, row hc - 4 for row hc
+    // (three rows: any row, it is not used); rows past hc belong to no step
+    const T *rows[M];
+    int cols[M];
+#pragma unroll
+    for (int q = 0; q < M; ++q) {
+        const int r = I0 - 1 + q;
+        const int src = r < 0 ? min(3, hc - 1) : (r == hc ? max(hc - 4, 0) : min(r, hc - 1));
+        rows[q] = c + (int64_t)src * pc;
+        cols[q] = wc;
+    }
+    T own[M][NV];
+    load_rows<T, VEC, NV, M>(rows, J0, cols, own);
+    T le[M], e1[M], e2[M], hd[M][4], tl[M][4];
+#pragma unroll
+    for (int q = 0; q < M; ++q) {
+        le[q] = left_edge<T>(rows[q], J0, wc);
+        e1[q] = right_edge<T>(rows[q], J0 + NV, wc);
+        e2[q] = right_edge<T>(rows[q], J0 + NV + 1, wc);
+        // both ends of the row, from the end inwards (wc == 3: the fourth is not used)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            hd[q][t] = rows[q][min(t, wc - 1)];
+            tl[q][t] = rows[q][max(wc - 1 - t, 0)];
+        }
+    }
+    T ev[M][NV], od[M][NV];
+#pragma unroll
+    for (int q = 0; q < M; ++q) {
+        const T gl = cubic_ghost<T>(wcubic, hd[q][0], hd[q][1], hd[q][2], hd[q][3]);
+        const T gr = cubic_ghost<T>(wcubic, tl[q][0], tl[q][1], tl[q][2], tl[q][3]);
+        // x[t] = c[J0 - 1 + t], t = 0 .. NV + 2, the ghosts at columns -1 and wc
+        T x[NV + 3];
+        x[0] = shift_from_left<T>(own[q][NV - 1], le[q]);
+#pragma unroll
+        for (int k = 0; k < NV; ++k) x[k + 1] = own[q][k];
+        x[NV + 1] = shift_from_right<T>(own[q][0], e1[q]);
+        // two columns on: the right lane's second element, or (one element per lane) its x[NV + 1]
+        if constexpr (NV >= 2) x[NV + 2] = shift_from_right<T>(own[q][1], e2[q]);
+        else x[NV + 2] = shift_from_right<T>(x[NV + 1], e2[q]);
+#pragma unroll
+        for (int t = 0; t < NV + 3; ++t) {
+            const int J = J0 - 1 + t;
+            x[t] = J == -1 ? gl : (J == wc ? gr : x[t]);
+        }
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            ev[q][k] = x[k + 1];
+            od[q][k] = cubic_mid<T>(x[k], x[k + 1], x[k + 2], x[k + 3]);
+        }
+    }
+    if (I0 == 0) {  // row -1 from the rows 0, 1, 2 and 3
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            ev[0][k] = cubic_ghost<T>(hcubic, ev[1][k], ev[2][k], ev[3][k], ev[0][k]);
+            od[0][k] = cubic_ghost<T>(hcubic, od[1][k], od[2][k], od[3][k], od[0][k]);
+        }
+    }
+#pragma unroll
+    for (int q = 3; q < M; ++q) {
+        if (I0 - 1 + q == hc) {  // row hc from the rows hc - 1, hc - 2, hc - 3 and hc - 4
+#pragma unroll
+            for (int k = 0; k < NV; ++k) {
+                ev[q][k] = cubic_ghost<T>(hcubic, ev[q - 1][k], ev[q - 2][k], ev[q - 3][k], ev[q][k]);
+                od[q][k] = cubic_ghost<T>(hcubic, od[q - 1][k], od[q - 2][k], od[q - 3][k], od[q][k]);
+            }
+        }
+    }
+    // fine row i: columns 2J get ev, columns 2J + 1 get od; interior only
+    auto put_row = [&](int i, const T(&pe)[NV], const T(&po)[NV]) {
+        T *row = u + (int64_t)i * pu;
+        T a[2][NV];
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            a[(2 * k) / NV][(2 * k) % NV] = pe[k];
+            a[(2 * k + 1) / NV][(2 * k + 1) % NV] = po[k];
+        }
+        store_n<T, VEC, NV>(row, f0, 1, w - 2, a[0]);
+        store_n<T, VEC, NV>(row, f0 + NV, 1, w - 2, a[1]);
+    };
+#pragma unroll
+    for (int s = 0; s < R; ++s) {
+        const int I = I0 + s;  // block-uniform
+        if (I >= hc - 1) break;
+        if (I >= 1) put_row(2 * I, ev[s + 1], od[s + 1]);  // fine row 0 is boundary
+        T mv[NV], md[NV];
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            mv[k] = cubic_mid<T>(ev[s][k], ev[s + 1][k], ev[s + 2][k], ev[s + 3][k]);
+            md[k] = cubic_mid<T>(od[s][k], od[s + 1][k], od[s + 2][k], od[s + 3][k]);
+        }
+        put_row(2 * I + 1, mv, md);
+    }
+}
+
 template <typename T>
 int launch_mg_residual(const T *u, const T *b, T *r, int rows, int cols, int pu, int pb, int pr, T *resid,
                        void *stream) {
@@ -260,6 +404,32 @@ int launch_mg_prolong(const T *e, T *u, int hc, int wc, int pe, int pu, void *st
     return MPX_OK;
 }
 
+template <typename T>
+int launch_mg_prolong_cubic(const T *c, T *u, int hc, int wc, int pc, int pu, void *stream) {
+    MPX_CHECK_ARG(c && u, "null pointer");
+    MPX_CHECK_ARG(hc >= 3 && wc >= 3 && wc < (1 << 29) && hc < (1 << 29) && pc >= wc && pu >= 2 * wc - 1,
+                  "bad grid geometry");
+    const bool vec = mg_vec<T>({c, u}, {pc, pu});
+    const int lanes = vec ? (wc + JVec<T>::n - 1) / JVec<T>::n : wc;
+    const int rpl = mg_rows_per_lane(lanes, hc - 1, kMgCubicRows);
+    const dim3 blk(256), grd((lanes + 255) / 256, (hc - 1 + rpl - 1) / rpl);
+    auto go = [&](auto vc, auto rc) {
+        hipLaunchKernelGGL((mg_prolong_cubic_kernel<T, decltype(vc)::value, decltype(rc)::value>), grd, blk, 0,
+                           as_stream(stream), c, u, hc, wc, pc, pu);
+    };
+    using R1 = std::integral_constant<int, 1>;
+    using R2 = std::integral_constant<int, kMgCubicRows>;
+    if (vec) {
+        if (rpl == 1) go(std::true_type{}, R1{});
+        else go(std::true_type{}, R2{});
+    } else {
+        if (rpl == 1) go(std::false_type{}, R1{});
+        else go(std::false_type{}, R2{});
+    }
+    MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
+    return MPX_OK;
+}
+
 }  // namespace
 MPX_MODULE_ANCHOR(multigrid)
 
@@ -291,4 +461,14 @@ extern "C" int mpx_mg_prolong_add_f64(const double *e, double *u, int hc, int wc
 
 extern "C" int mpx_mg_prolong_add_f32(const float *e, float *u, int hc, int wc, int pitch_e, int pitch_u, void *stream) {
     return mpx::launch_mg_prolong<float>(e, u, hc, wc, pitch_e, pitch_u, stream);
+}
+
+extern "C" int mpx_mg_prolong_cubic_f64(const double *c, double *u, int hc, int wc, int pitch_c, int pitch_u,
+                                        void *stream) {
+    return mpx::launch_mg_prolong_cubic<double>(c, u, hc, wc, pitch_c, pitch_u, stream);
+}
+
+extern "C" int mpx_mg_prolong_cubic_f32(const float *c, float *u, int hc, int wc, int pitch_c, int pitch_u,
+                                        void *stream) {
+    return mpx::launch_mg_prolong_cubic<float>(c, u, hc, wc, pitch_c, pitch_u, stream);
 }

@@ -6,13 +6,13 @@ solve of the same problem in the same session.
 
   python tools/bench_multigrid.py [--rows 2047] [--cols 2049] [--fp32]
                                   [--tol 1e-8] [--reps 20] [--no-solve]
-                                  [--tail-points N] [--tail-table]
+                                  [--tail-points N] [--tail-table] [--fmg]
 
 Per-kernel times: device events around single launches, median over --reps
 launches that rotate through buffer sets larger than the 256 MiB Infinity
 Cache together, so no launch finds its input cached. The rates count the words
 the algorithm needs per fine point: relax 3, residual 3, restrict 1.25,
-prolong-add 2.25. ``rhs_sweep_even`` is ops.jacobi_sweep(rhs=) on the
+prolong-add 2.25, prolong-cubic 1.25. ``rhs_sweep_even`` is ops.jacobi_sweep(rhs=) on the
 (rows + 2, cols - 1) grid, whose even width takes the wave-strip kernel: the
 gap to ``relax`` is what the odd width costs. ``below_level2_share`` is the
 time of the sub-cycle from level 2 down over the whole cycle (launch-bound).
@@ -21,6 +21,16 @@ time of the sub-cycle from level 2 down over the whole cycle (launch-bound).
 level launched; default: the model's measured threshold); the JSON line carries
 ``tail_points``, ``tail_level`` and ``launches_per_cycle``. ``--tail-table``: per
 level, the sub-cycle from that level down, launched and fused (``tail_table``).
+
+``--fmg``: full multigrid on the manufactured problem u = sin(3x + 0.4) e^y
+(-Laplace(u) = 8 u, nonzero Dirichlet values, h = 1 / (cols - 1)), under the
+key ``fmg``: the time of ``fmg()`` (median over --reps calls, host clock, each
+ends in the residual read), max|u_fmg - u|, and rho = max|u_fmg - u_h| /
+max|u_h - u| with u_h from 25 fp64 cycles; next to it, in the same session,
+``solve(tol)`` of the same problem from a zero interior (time, cycles and its
+max|u - exact|), one ``cycle()``, and ``fmg()`` of the level-1 grid alone
+(``below_level0_ms``: what ``fmg()`` spends below level 0, but for one
+restriction and the boundary injection).
 
 Prints one JSON line.
 """
@@ -86,6 +96,7 @@ def kernel_times(rows, cols, dt, reps, dev):
         c = [s._lv[1] for s in sets]
         out["restrict"] = (median_us(lambda k: ops.mg_restrict(f[k].r, c[k].b), nsets, reps, dev), 1.25)
         out["prolong_add"] = (median_us(lambda k: ops.mg_prolong_add_(c[k].u, f[k].u), nsets, reps, dev), 2.25)
+        out["prolong_cubic"] = (median_us(lambda k: ops.mg_prolong_cubic(c[k].u, f[k].u), nsets, reps, dev), 1.25)
     del sets, f
     we = w - 1  # the even width next to it: the wave-strip kernel
     ev = [[torch.rand((h, we), dtype=dt, device=dev) for _ in range(3)] for _ in range(nsets)]
@@ -133,6 +144,78 @@ def tail_table(rows, cols, dt, reps, max_points, dev):
     return rows_out
 
 
+def manufactured(rows, cols):
+    """u = sin(3x + 0.4) e^y on the (rows + 2, cols) grid, h = 1 / (cols - 1); and h."""
+    h = 1.0 / (cols - 1)
+    y = torch.arange(rows + 2, dtype=torch.float64).unsqueeze(1) * h
+    x = torch.arange(cols, dtype=torch.float64).unsqueeze(0) * h
+    return torch.sin(3.0 * x + 0.4) * torch.exp(y), h
+
+
+def fmg_report(rows, cols, dt, reps, tol, tail_points, dev):
+    def problem(r, c, dtype):
+        m = PoissonMultigrid(r, c, dtype=dtype, device=dev, tail_points=tail_points)
+        u, h = manufactured(r, c)
+        u = u.to(dev)
+        m.set_rhs(tensor=(8.0 * h * h * u)[1:-1])
+        m.u.copy_(u)
+        m.u[1:-1, 1:-1] = 0.0
+        m._lv[0].un.copy_(m.u)
+        return m, u
+
+    def timed(fn, n):
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize(dev)
+            ts.append(time.perf_counter() - t0)
+        return statistics.median(ts) * 1e3
+
+    out = {}
+    m, exact = problem(rows, cols, dt)
+    for _ in range(3):
+        m.fmg()
+    out["fmg_ms"] = round(timed(m.fmg, reps), 4)
+    ufmg = m.u.to(torch.float64).clone()
+    out["fmg_residual"] = m.last_residual
+    out["fmg_error"] = float((ufmg - exact).abs().max())
+    m.fmg(2)
+    out["fmg2_ms"] = round(timed(lambda: m.fmg(2), reps), 4)
+    out["fmg2_error"] = float((m.u.to(torch.float64) - exact).abs().max())
+    ufmg2 = m.u.to(torch.float64).clone()
+    out["cycle_ms"] = round(timed(m.cycle, reps), 4)
+    del m
+    # solve(tol) from a zero interior: the second solve, on kernels and buffers already warm
+    for k in range(2):
+        s, _ = problem(rows, cols, dt)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        n = s.solve(tol)
+        torch.cuda.synchronize(dev)
+        out.update({"solve_ms": round((time.perf_counter() - t0) * 1e3, 3), "solve_cycles": n,
+                    "solve_residual": s.last_residual, "solve_error": float((s.u.to(torch.float64) - exact).abs().max())})
+        del s
+    if len(PoissonMultigrid.level_shapes(rows, cols)) > 1:
+        c, _ = problem((rows + 2 + 1) // 2 - 2, (cols + 1) // 2, dt)
+        for _ in range(3):
+            c.fmg()
+        out["below_level0_ms"] = round(timed(c.fmg, reps), 4)
+        del c
+    # the discrete solution in fp64, whatever the dtype timed
+    d, _ = problem(rows, cols, torch.float64)
+    for _ in range(25):
+        d.cycle()
+    uh = d.u
+    disc = float((uh - exact).abs().max())
+    out.update({"discretisation_error": disc, "uh_residual": d.last_residual,
+                "rho": round(float((ufmg - uh).abs().max()) / disc, 4),
+                "rho2": round(float((ufmg2 - uh).abs().max()) / disc, 4)})
+    out["fmg_over_cycle"] = round(out["fmg_ms"] / out["cycle_ms"], 3)
+    return out
+
+
 def main() -> int:
     p = argparse.ArgumentParser()
     p.add_argument("--rows", type=int, default=2047)
@@ -147,6 +230,8 @@ def main() -> int:
     p.add_argument("--tail-table", action="store_true",
                    help="time the sub-cycle from every level of at most --tail-table-max points down, launched and fused")
     p.add_argument("--tail-table-max", type=int, default=263169)
+    p.add_argument("--fmg", action="store_true",
+                   help="full multigrid on the manufactured problem next to solve(tol) and cycle() (key fmg)")
     p.add_argument("--max-jacobi-iters", type=int, default=200000)
     a = p.parse_args()
     if not torch.cuda.is_available():
@@ -209,13 +294,15 @@ def main() -> int:
         solve["jacobi_over_multigrid"] = round(solve["jacobi_solve_ms"] / solve["solve_ms"], 2)
         solve["max_abs_difference"] = float((s.u - j.u).abs().max())
 
+    fmg = fmg_report(rows, cols, dt, a.reps, a.tol, a.tail_points, dev) if a.fmg else None
+
     print(json.dumps({
         "metric": "2-D Poisson multigrid V(2,2) cycle time on one MI355X",
         "value": round(cycle_ms, 4), "unit": "ms/cycle", "higher_is_better": False,
         "grid": [rows + 2, cols], "dtype": "fp32" if a.fp32 else "fp64", "levels": len(mg.levels),
         "coarsest": list(mg.levels[-1]), "reps": a.reps, "tol": a.tol,
         "below_level2_share": None if share is None else round(share, 3),
-        **plan, "tail_table": table, "level0_kernels": kern, **solve}), flush=True)
+        **plan, "tail_table": table, "level0_kernels": kern, "fmg": fmg, **solve}), flush=True)
     return 0
 
 
