@@ -144,7 +144,10 @@ _SIGNATURES = {
     "mpx_mg3_restrict_f32": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64, c_vp]),
     "mpx_mg3_prolong_add_f64": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64, c_vp]),
     "mpx_mg3_prolong_add_f32": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64, c_vp]),
+    "mpx_mg3_prolong_cubic_f64": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64, c_vp]),
+    "mpx_mg3_prolong_cubic_f32": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64, c_vp]),
     "mpx_mg3_walk": (c_int, [_ip]),
+    "mpx_mg3_cubic_walk": (c_int, [_ip]),
     # the coarse levels of a V-cycle in one kernel: (levels, n, nu1, nu2, coarse_sweeps, omega, stream)
     "mpx_mg_tail_f64": (c_int, [c_vp, c_int, c_int, c_int, c_int, ctypes.c_double, c_vp]),
     "mpx_mg_tail_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, ctypes.c_double, c_vp]),
@@ -156,6 +159,7 @@ _SIGNATURES = {
                                                    c_int, c_i64]),
     "mpx_cpu_mg3_restrict_f64": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64]),
     "mpx_cpu_mg3_prolong_add_f64": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64]),
+    "mpx_cpu_mg3_prolong_cubic_f64": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_int, c_i64]),
     "mpx_cpu_threads": (c_int, []),
     "mpx_cpu_vsub_f64": (None, [c_vp, c_vp, c_vp, c_i64]),
     "mpx_cpu_vsub_f32": (None, [c_vp, c_vp, c_vp, c_i64]),

@@ -7,7 +7,8 @@ from .edge import ConvLauncher, conv, conv_rows, roberts, roberts_rgb
 from .filters import Filter, get_filter, list_filters
 from .multigrid import (jacobi_relax, mg_prolong_add_, mg_prolong_cubic, mg_residual, mg_restrict, mg_tail,
                         tail_sweeps)
-from .multigrid3d import jacobi3d_relax, mg3_prolong_add_, mg3_residual, mg3_restrict, mg3_tail, mg3_walk
+from .multigrid3d import (jacobi3d_relax, mg3_cubic_walk, mg3_prolong_add_, mg3_prolong_cubic, mg3_residual, mg3_restrict,
+                          mg3_tail, mg3_walk)
 from .sort import argsort, sort, sort_, sort_pairs_
 from .stencil import jacobi3d_sweep, jacobi3d_tile, jacobi_sweep
 from .vector import vsub
@@ -36,6 +37,8 @@ __all__ = [
     "mg3_residual",
     "mg3_restrict",
     "mg3_prolong_add_",
+    "mg3_prolong_cubic",
+    "mg3_cubic_walk",
     "mg3_walk",
     "mg_tail",
     "mg3_tail",

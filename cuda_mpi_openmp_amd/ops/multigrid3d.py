@@ -58,6 +58,15 @@ def mg3_walk() -> dict:
     return {"rows": out[0], "restrict_planes": out[1], "prolong_planes": out[2], "min_waves": out[3], "waves": out[4]}
 
 
+def mg3_cubic_walk() -> dict:
+    """The walk of ``mg3_prolong_cubic``'s launches: {"planes": coarse planes
+    walked per lane, "min_waves": the wave count below which a launch halves
+    that walk (``mg3_walk``'s), "waves": waves (coarse rows) per workgroup}."""
+    out = _native.i32_array([0, 0, 0])
+    _native.check(_native.lib().mpx_mg3_cubic_walk(out))
+    return {"planes": out[0], "min_waves": out[1], "waves": out[2]}
+
+
 def jacobi3d_relax(u: torch.Tensor, un: torch.Tensor, k0: int, k1: int, omega: float,
                    resid: Optional[torch.Tensor] = None, rhs: Optional[torch.Tensor] = None) -> Optional[float]:
     """Damped 3-D Jacobi sweep over planes [k0, k1): with s the plain or Poisson
@@ -176,6 +185,33 @@ def mg3_prolong_add_(e: torch.Tensor, u: torch.Tensor) -> None:
         return
     if L.mpx_cpu_mg3_prolong_add_f64(e.data_ptr(), u.data_ptr(), dc, hc, wc, pe, se, pu, su) != 0:
         raise ValueError("mg3_prolong_add_: bad arguments")
+
+
+def mg3_prolong_cubic(c: torch.Tensor, u: torch.Tensor) -> None:
+    """Tricubic interpolation of the coarse ``c`` written over the fine
+    interior of ``u`` (the interpolant of full multigrid; ``u``'s interior on
+    entry is ignored). Separable, from ``mg_prolong_cubic``'s 1-D rule
+    unchanged (even points copy c, the midpoint between K and K + 1 is
+    ``(a + (a - o) * 0.125) * 0.5`` with a = c[K] + c[K+1] and
+    o = c[K-1] + c[K+2], cubic ghosts for n >= 4, parabola ghosts for n = 3):
+    along x in every coarse row, then along y down the columns of those rows
+    (ghost rows element by element from the interpolated rows), then along z
+    through the interpolated planes (ghost planes element by element from
+    them). The interior of fine plane 2K, 1 <= K <= Dc - 2, therefore equals
+    ``mg_prolong_cubic`` of coarse plane K bit for bit. c's boundary is read
+    (the coarse Dirichlet values); u's boundary is not written. Needs a coarse
+    grid of at least 3 x 3 x 3."""
+    (pu, su), (pc, sc), dc, hc, wc = _coarse3_of(u, c, "u", "c")
+    if min(dc, hc, wc) < 3:
+        raise ValueError("mg3_prolong_cubic needs a coarse grid of at least 3 x 3 x 3")
+    _check_dtype(u, "mg3_prolong_cubic")
+    L = _native.lib()
+    if u.is_cuda:
+        fn = L.mpx_mg3_prolong_cubic_f64 if u.dtype == torch.float64 else L.mpx_mg3_prolong_cubic_f32
+        _native.check(fn(c.data_ptr(), u.data_ptr(), dc, hc, wc, pc, sc, pu, su, _native.stream_of(u)))
+        return
+    if L.mpx_cpu_mg3_prolong_cubic_f64(c.data_ptr(), u.data_ptr(), dc, hc, wc, pc, sc, pu, su) != 0:
+        raise ValueError("mg3_prolong_cubic: bad arguments")
 
 
 # ---------------------------------------------------------------------------

@@ -344,3 +344,21 @@ def mg3_prolong_add(e: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
     out = u.clone()
     out[1:-1, 1:-1, 1:-1] = u[1:-1, 1:-1, 1:-1] + X[1:-1, 1:-1, 1:-1]
     return out
+
+
+def mg3_prolong_cubic(c: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+    """u with its interior replaced by the tricubic interpolation of the coarse
+    c, in u's dtype and the kernels' order: the 1-D rule of
+    ``ops.mg_prolong_cubic`` along x in every coarse row, then along y down the
+    columns of the interpolated rows, then along z through the interpolated
+    planes; u's boundary is returned unchanged."""
+    u = u.cpu()
+    c = c.cpu().to(u.dtype)
+    if c.dim() != 3 or min(c.shape) < 3 or u.shape != tuple(2 * n - 1 for n in c.shape):
+        raise ValueError("u must be (2 Dc - 1, 2 Hc - 1, 2 Wc - 1) with Dc, Hc, Wc >= 3")
+    full = _cubic_rows(c)
+    full = _cubic_rows(full.transpose(1, 2)).transpose(1, 2)
+    full = _cubic_rows(full.transpose(0, 2)).transpose(0, 2)
+    out = u.clone()
+    out[1:-1, 1:-1, 1:-1] = full[1:-1, 1:-1, 1:-1]
+    return out

@@ -491,7 +491,18 @@ int mpx_jacobi3d_tile(int fp64, int rhs, int accel, int *out);
  *     X[k][i][j] = Y[k][i][I] for j = 2I,  Y[k][i][I] + Y[k][i][I+1] for j = 2I + 1
  *     u[k][i][j] += X[k][i][j] * 0.5^(number of odd coordinates among k, i, j)
  *   with no multiply when that factor is 1. e's boundary is read; u's boundary
- *   is not written. dc, hc, wc >= 2. */
+ *   is not written. dc, hc, wc >= 2.
+ * mg3_prolong_cubic (tricubic interpolation of the coarse c written over u's
+ *   interior; the interpolant of full multigrid), separable, built from the 1-D
+ *   rule of prolong_cubic above, unchanged (midpoint (a + (a - o) * 0.125) * 0.5,
+ *   cubic ghosts for n >= 4, parabola ghosts for n == 3): the rule runs along x
+ *   in every coarse row, which gives dc x hc rows of width W; then along y down
+ *   the columns of those rows, the ghost rows formed element by element from
+ *   the interpolated rows, which gives dc planes of H x W; then along z through
+ *   those planes, the ghost planes formed element by element from them. So the
+ *   interior of fine plane 2K, 1 <= K <= dc - 2, is mg_prolong_cubic of coarse
+ *   plane K bit for bit. c's boundary is read (the coarse Dirichlet values);
+ *   only u's interior is written. dc, hc, wc >= 3. */
 int mpx_jacobi3d_relax_f64(const double *u, const double *b, double *un, int d, int ny, int nx, int pitch,
                            int64_t plane, int k0, int k1, double omega, double *resid, void *stream);
 int mpx_jacobi3d_relax_f32(const float *u, const float *b, float *un, int d, int ny, int nx, int pitch, int64_t plane,
@@ -509,6 +520,10 @@ int mpx_mg3_prolong_add_f64(const double *e, double *u, int dc, int hc, int wc, 
                             int pitch_u, int64_t plane_u, void *stream);
 int mpx_mg3_prolong_add_f32(const float *e, float *u, int dc, int hc, int wc, int pitch_e, int64_t plane_e, int pitch_u,
                             int64_t plane_u, void *stream);
+int mpx_mg3_prolong_cubic_f64(const double *c, double *u, int dc, int hc, int wc, int pitch_c, int64_t plane_c,
+                              int pitch_u, int64_t plane_u, void *stream);
+int mpx_mg3_prolong_cubic_f32(const float *c, float *u, int dc, int hc, int wc, int pitch_c, int64_t plane_c,
+                              int pitch_u, int64_t plane_u, void *stream);
 /* The walks of the 3-D multigrid launches: out[0] = rows of a plane walked per
  * lane by relax / residual, out[1] / out[2] = coarse planes walked per lane by
  * the restriction / the prolongation, out[3] = the wave count below which a
@@ -516,6 +531,10 @@ int mpx_mg3_prolong_add_f32(const float *e, float *u, int dc, int hc, int wc, in
  * out[4] = waves per workgroup (row blocks of the stencil walk, coarse rows of
  * the transfers). out: 5 ints. */
 int mpx_mg3_walk(int *out);
+/* The walk of mg3_prolong_cubic: out[0] = coarse planes walked per lane,
+ * out[1] = the wave count below which a launch halves that walk (mpx_mg3_walk's
+ * out[3]), out[2] = waves (coarse rows) per workgroup. out: 3 ints. */
+int mpx_mg3_cubic_walk(int *out);
 
 /* The coarse levels of a V-cycle in one kernel (native/src/kernels/mg_tail.hip):
  * one workgroup runs, from lv[0] down to lv[n - 1] and back up, what the launched
@@ -640,6 +659,8 @@ double mpx_cpu_mg3_residual_f64(const double *u, const double *b, double *r, int
                                 int64_t plane_u, int pitch_b, int64_t plane_b, int pitch_r, int64_t plane_r);
 int mpx_cpu_mg3_restrict_f64(const double *r, double *bc, int dc, int hc, int wc, int pitch_r, int64_t plane_r,
                              int pitch_bc, int64_t plane_bc);
+int mpx_cpu_mg3_prolong_cubic_f64(const double *c, double *u, int dc, int hc, int wc, int pitch_c, int64_t plane_c,
+                                  int pitch_u, int64_t plane_u);
 int mpx_cpu_mg3_prolong_add_f64(const double *e, double *u, int dc, int hc, int wc, int pitch_e, int64_t plane_e,
                                 int pitch_u, int64_t plane_u);
 void mpx_cpu_sort(void *data, int64_t n, int dtype);

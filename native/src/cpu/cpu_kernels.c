@@ -592,6 +592,29 @@ static inline double cubic_row(const double *c, int n, int j) {
     return cubic_mid(cm, c[K], c[K + 1], cp);
 }
 
+/* element (i, j) of the 2-D rule applied to an hc x wc grid: cubic_row along the
+ * coarse rows, then the 1-D rule down column j of the interpolated rows, the
+ * ghost rows from the first / last four of them */
+static inline double cubic_plane(const double *c, int hc, int wc, int pitch_c, int i, int j) {
+    const int K = i / 2;
+    if (!(i & 1)) return cubic_row(c + (int64_t)K * pitch_c, wc, j);
+    double v[4];
+    for (int q = 0; q < 4; ++q) {
+        const int I = K - 1 + q;
+        if (I >= 0 && I < hc) {
+            v[q] = cubic_row(c + (int64_t)I * pitch_c, wc, j);
+        } else {
+            double g[4];
+            for (int t = 0; t < 4; ++t) {
+                const int R = t < 3 || hc >= 4 ? t : 0; /* hc == 3: the fourth is not used */
+                g[t] = cubic_row(c + (int64_t)(I < 0 ? R : hc - 1 - R) * pitch_c, wc, j);
+            }
+            v[q] = cubic_ghost(hc, g[0], g[1], g[2], g[3]);
+        }
+    }
+    return cubic_mid(v[0], v[1], v[2], v[3]);
+}
+
 int mpx_cpu_mg_prolong_cubic_f64(const double *c, double *u, int hc, int wc, int pitch_c, int pitch_u) {
     int i;
     if (!c || !u || hc < 3 || wc < 3 || hc >= (1 << 29) || wc >= (1 << 29) || pitch_c < wc || pitch_u < 2 * wc - 1)
@@ -599,30 +622,8 @@ int mpx_cpu_mg_prolong_cubic_f64(const double *c, double *u, int hc, int wc, int
     const int h = 2 * hc - 1, w = 2 * wc - 1;
 #pragma omp parallel for schedule(static)
     for (i = 1; i < h - 1; ++i) {
-        const int K = i / 2;
         double *o = u + (int64_t)i * pitch_u;
-        for (int j = 1; j < w - 1; ++j) {
-            if (!(i & 1)) {
-                o[j] = cubic_row(c + (int64_t)K * pitch_c, wc, j);
-                continue;
-            }
-            /* column j of the interpolated rows K - 1 .. K + 2, the ghost rows from the first / last four */
-            double v[4];
-            for (int q = 0; q < 4; ++q) {
-                const int I = K - 1 + q;
-                if (I >= 0 && I < hc) {
-                    v[q] = cubic_row(c + (int64_t)I * pitch_c, wc, j);
-                } else {
-                    double g[4];
-                    for (int t = 0; t < 4; ++t) {
-                        const int R = t < 3 || hc >= 4 ? t : 0; /* hc == 3: the fourth is not used */
-                        g[t] = cubic_row(c + (int64_t)(I < 0 ? R : hc - 1 - R) * pitch_c, wc, j);
-                    }
-                    v[q] = cubic_ghost(hc, g[0], g[1], g[2], g[3]);
-                }
-            }
-            o[j] = cubic_mid(v[0], v[1], v[2], v[3]);
-        }
+        for (int j = 1; j < w - 1; ++j) o[j] = cubic_plane(c, hc, wc, pitch_c, i, j);
     }
     return 0;
 }
@@ -839,6 +840,47 @@ int mpx_cpu_mg3_prolong_add_f64(const double *e, double *u, int dc, int hc, int 
                     x = y0;
                 }
                 o[j] = odd ? o[j] + x * scale[odd] : o[j] + x;
+            }
+        }
+    }
+    return 0;
+}
+
+/* mg3_prolong_cubic (capi.h): cubic_plane in every coarse plane, then the 1-D
+ * rule down z through the interpolated planes, the ghost planes element by
+ * element from the first / last four of them */
+int mpx_cpu_mg3_prolong_cubic_f64(const double *c, double *u, int dc, int hc, int wc, int pitch_c, int64_t plane_c,
+                                  int pitch_u, int64_t plane_u) {
+    int k;
+    if (!c || !u || !mg3_coarse_ok(dc, hc, wc) || dc < 3 || hc < 3 || wc < 3 ||
+        !mg3_strides_ok(hc, wc, pitch_c, plane_c) || !mg3_strides_ok(2 * hc - 1, 2 * wc - 1, pitch_u, plane_u))
+        return -1;
+    const int d = 2 * dc - 1, h = 2 * hc - 1, w = 2 * wc - 1;
+#pragma omp parallel for schedule(static)
+    for (k = 1; k < d - 1; ++k) {
+        const int K = k / 2;
+        for (int i = 1; i < h - 1; ++i) {
+            double *o = u + (int64_t)k * plane_u + (int64_t)i * pitch_u;
+            for (int j = 1; j < w - 1; ++j) {
+                if (!(k & 1)) {
+                    o[j] = cubic_plane(c + (int64_t)K * plane_c, hc, wc, pitch_c, i, j);
+                    continue;
+                }
+                double v[4];
+                for (int q = 0; q < 4; ++q) {
+                    const int P = K - 1 + q;
+                    if (P >= 0 && P < dc) {
+                        v[q] = cubic_plane(c + (int64_t)P * plane_c, hc, wc, pitch_c, i, j);
+                    } else {
+                        double g[4];
+                        for (int t = 0; t < 4; ++t) {
+                            const int R = t < 3 || dc >= 4 ? t : 0; /* dc == 3: the fourth is not used */
+                            g[t] = cubic_plane(c + (int64_t)(P < 0 ? R : dc - 1 - R) * plane_c, hc, wc, pitch_c, i, j);
+                        }
+                        v[q] = cubic_ghost(dc, g[0], g[1], g[2], g[3]);
+                    }
+                }
+                o[j] = cubic_mid(v[0], v[1], v[2], v[3]);
             }
         }
     }

@@ -209,28 +209,6 @@ __global__ __launch_bounds__(256) void mg_prolong_kernel(const T *__restrict__ e
     }
 }
 
-// the midpoint of the cubic through four equidistant values (weights
-// (-1, 9, 9, -1) / 16, the scale factors exact) and the value one step before
-// c0 on the cubic through c0..c3 (CUBIC) or the parabola through c0..c2
-template <typename T>
-__device__ __forceinline__ T cubic_mid(T cm, T c0, T c1, T c2) {
-    const T a = c0 + c1;
-    const T o = cm + c2;
-    const T d = a - o;
-    const T t = a + d * (T)0.125;
-    return t * (T)0.5;
-}
-
-template <typename T>
-__device__ __forceinline__ T cubic_ghost(bool cubic, T c0, T c1, T c2, T c3) {
-    const T s = c0 + c2;
-    const T q = s * (T)4 - c3;
-    const T g4 = q - c1 * (T)6;
-    const T d = c0 - c1;
-    const T g3 = d * (T)3 + c2;
-    return cubic ? g4 : g3;
-}
-
 // cubic interpolation of the coarse c written to the fine interior of u (the
 // FMG interpolant). A lane owns the coarse columns [J0, J0 + NV) and the fine
 // columns [2 J0, 2 J0 + 2 NV) below them. A coarse row is interpolated along

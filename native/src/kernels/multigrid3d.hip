@@ -8,8 +8,9 @@
 // row pitch and plane stride (elements; plane offsets are 64-bit); padding is
 // never read and never written.
 //
-// MI355X design: all four kernels are HBM-bound (3 / 3 / 1.125 / 2.125 words
-// per fine point), the shape is multigrid.hip's one dimension up:
+// MI355X design: all five kernels are HBM-bound (relax 3, residual 3, restrict
+// 1.125, prolong-add 2.125, cubic prolong 1.125 words per fine point), the shape
+// is multigrid.hip's one dimension up:
 //   * a workgroup is 4 waves of 64 lanes in x; a lane owns one 16-B vector of
 //     the narrower grid per row (relax, residual: of u; restrict and prolong: of
 //     the coarse grid, and with it the two fine vectors below it), so the
@@ -25,11 +26,18 @@
 //     coarse planes. Restriction keeps the in-plane result of fine plane 2K + 1
 //     for coarse plane K + 1; prolongation keeps the two coarse rows of plane
 //     K + 1. The rows shared between neighbouring J are re-read by the next wave
-//     of the same workgroup;
+//     of the same workgroup. The cubic prolongation (full multigrid) keeps the
+//     in-plane interpolated fine rows 2J and 2J + 1 of the four coarse planes
+//     K - 1 .. K + 2 (fp64: 16 vectors), fetches the coarse rows J - 1 .. J + 2
+//     of one new plane per step and stores every fine point once. That state
+//     costs registers (fp64: 158 VGPRs, three waves per SIMD), and the kernel
+//     runs at half of prolong-add's rate for half its bytes
+//     (profiles/multigrid3d.md);
 //   * all loads of a step (relax: the four streams of a row; restrict: the six
 //     vectors of a fine plane; prolong: the coarse rows, then the fine rows of a
-//     plane) go through one load_rows group, issued back to back and waited for
-//     once; load_n row by row costs a full memory latency per load;
+//     plane; cubic prolong: the four coarse rows of a plane) go through one
+//     load_rows group, issued back to back and waited for once; load_n row by
+//     row costs a full memory latency per load;
 //   * a launch too small to fill the device shortens its walks (mg3_walk). The
 //     walks are short anyway: longer ones measured slower (profiles/multigrid3d.md);
 //   * known cost: a row of 2^n + 1 elements ends in a wave with one active lane
@@ -58,6 +66,22 @@ constexpr int kMg3Waves = 4;  // waves (rows of the stencil walk, coarse rows of
 struct Mg3Walk {
     int rows = 4, restrict_planes = 4, prolong_planes = 2, min_waves = 8192;
 };
+
+// coarse planes walked per lane by the cubic prolongation: a block of R planes
+// fetches R + 3, so the walk is longer than the other transfers'.
+// MPX_MG3_CUBIC_WALK="planes" replaces it for A/B measurements; min_waves is
+// Mg3Walk's.
+inline int mg3_cubic_planes() {
+    static const int planes = [] {
+        int v = 8;
+        if (const char *s = std::getenv("MPX_MG3_CUBIC_WALK")) {
+            int a = 0;
+            if (std::sscanf(s, "%d", &a) == 1 && a >= 1 && a <= 64) v = a;
+        }
+        return v;
+    }();
+    return planes;
+}
 
 inline const Mg3Walk &mg3_walk_config() {
     static const Mg3Walk w = [] {
@@ -354,6 +378,165 @@ __global__ __launch_bounds__(64 * kMg3Waves) void mg3_prolong_kernel(const T *__
     }
 }
 
+// tricubic interpolation of the coarse c written to the fine interior of u (the
+// FMG interpolant): mg_prolong_cubic_kernel's rule in every coarse plane, then
+// the same 1-D rule down z through the interpolated planes. A lane owns the
+// coarse columns [I0, I0 + NV) and the fine columns [2 I0, 2 I0 + 2 NV) below
+// them, a wave the coarse rows J - 1 .. J + 2 and with them the fine rows 2J and
+// 2J + 1. plane() fetches those four rows of one coarse plane in one group of
+// loads, interpolates each along x (c[I0 - 1], c[I0 + NV] and c[I0 + NV + 1]
+// come from the neighbouring lanes by wave shifts, the ghost columns -1 and wc
+// from the ends of the row in the workgroups that hold them), forms the ghost
+// row -1 or hc from the interpolated rows and leaves the two fine rows of the
+// plane: q[0] = fine row 2J, q[1] = fine row 2J + 1, each as the lane's two fine
+// vectors. The march keeps them for the coarse planes K - 1 .. K + 2: fine plane
+// 2K is plane K's rows, fine plane 2K + 1 the midpoints of the four. The ghost
+// planes -1 and dc are formed element by element from the interpolated planes;
+// their slot first fetches the fourth plane the ghost is made of. All row,
+// plane and ghost conditions are wave-uniform.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(64 * kMg3Waves) void mg3_prolong_cubic_kernel(const T *__restrict__ c, T *__restrict__ u,
+                                                                            int dc, int hc, int wc, int pc, int64_t sc,
+                                                                            int pu, int64_t su, int nxb, int njb,
+                                                                            int kpl) {
+    constexpr int NV = VEC ? JVec<T>::n : 1;
+    const unsigned bid = blockIdx.x;
+    const int xb = (int)(bid % (unsigned)nxb);
+    const unsigned t = bid / (unsigned)nxb;
+    const int jb = (int)(t % (unsigned)njb);
+    const int kb = (int)(t / (unsigned)njb);
+    const int I0 = NV * (xb * 64 + (int)threadIdx.x);
+    const int f0 = 2 * I0;
+    const int w = 2 * wc - 1;
+    const int J = jb * kMg3Waves + (int)threadIdx.y;  // wave-uniform
+    if (J >= hc - 1) return;
+    const int K0 = kb * kpl;
+    const int K1 = min(K0 + kpl, dc - 1);
+    const bool wcubic = wc >= 4, hcubic = hc >= 4, dcubic = dc >= 4;
+    // the waves whose lanes see column -1 / column wc (block-uniform)
+    const bool at_left = xb == 0, at_right = NV * (xb * 64 + 64) + 1 >= wc;
+    // slot s holds coarse row J - 1 + s. Where that is a ghost row the slot fetches
+    // the fourth row the ghost is made of: row 3 for row -1, row hc - 4 for row hc
+    // (three rows: any row, it is not used)
+    int64_t roff[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const int r = J - 1 + s;
+        const int src = r < 0 ? min(3, hc - 1) : (r == hc ? max(hc - 4, 0) : r);
+        roff[s] = (int64_t)src * pc;
+    }
+    auto plane = [&](int P, T (&q)[2][2][NV]) {
+        const T *base = c + (int64_t)P * sc;
+        const T *rows[4];
+        int cols[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            rows[s] = base + roff[s];
+            cols[s] = wc;
+        }
+        T own[4][NV];
+        load_rows<T, VEC, NV, 4>(rows, I0, cols, own);
+        T le[4], e1[4], e2[4], gl[4], gr[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            le[s] = left_edge<T>(rows[s], I0, wc);
+            e1[s] = right_edge<T>(rows[s], I0 + NV, wc);
+            e2[s] = right_edge<T>(rows[s], I0 + NV + 1, wc);
+            gl[s] = gr[s] = (T)0;
+        }
+        // the ghost columns, from the ends of the row inwards (wc == 3: the fourth is not used)
+        if (at_left) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                gl[s] = cubic_ghost<T>(wcubic, rows[s][0], rows[s][1], rows[s][2], rows[s][min(3, wc - 1)]);
+        }
+        if (at_right) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                gr[s] = cubic_ghost<T>(wcubic, rows[s][wc - 1], rows[s][wc - 2], rows[s][wc - 3], rows[s][max(wc - 4, 0)]);
+        }
+        // f[s]: row J - 1 + s interpolated along x, the lane's 2 NV fine columns
+        T f[4][2 * NV];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            // x[m] = c[I0 - 1 + m], m = 0 .. NV + 2, the ghosts at columns -1 and wc
+            T x[NV + 3];
+            x[0] = shift_from_left<T>(own[s][NV - 1], le[s]);
+#pragma unroll
+            for (int k = 0; k < NV; ++k) x[k + 1] = own[s][k];
+            x[NV + 1] = shift_from_right<T>(own[s][0], e1[s]);
+            // two columns on: the right lane's second element, or (one element per lane) its x[NV + 1]
+            if constexpr (NV >= 2) x[NV + 2] = shift_from_right<T>(own[s][1], e2[s]);
+            else x[NV + 2] = shift_from_right<T>(x[NV + 1], e2[s]);
+#pragma unroll
+            for (int m = 0; m < NV + 3; ++m) {
+                const int I = I0 - 1 + m;
+                x[m] = I == -1 ? gl[s] : (I == wc ? gr[s] : x[m]);
+            }
+#pragma unroll
+            for (int k = 0; k < NV; ++k) {
+                f[s][2 * k] = x[k + 1];
+                f[s][2 * k + 1] = cubic_mid<T>(x[k], x[k + 1], x[k + 2], x[k + 3]);
+            }
+        }
+        if (J == 0) {  // row -1 from the rows 0, 1, 2 and 3
+#pragma unroll
+            for (int e = 0; e < 2 * NV; ++e) f[0][e] = cubic_ghost<T>(hcubic, f[1][e], f[2][e], f[3][e], f[0][e]);
+        }
+        if (J + 2 == hc) {  // row hc from the rows hc - 1, hc - 2, hc - 3 and hc - 4
+#pragma unroll
+            for (int e = 0; e < 2 * NV; ++e) f[3][e] = cubic_ghost<T>(hcubic, f[2][e], f[1][e], f[0][e], f[3][e]);
+        }
+#pragma unroll
+        for (int e = 0; e < 2 * NV; ++e) {
+            q[0][e / NV][e % NV] = f[1][e];
+            q[1][e / NV][e % NV] = cubic_mid<T>(f[0][e], f[1][e], f[2][e], f[3][e]);
+        }
+    };
+    // fine plane k, rows 2J (row 0 is boundary) and 2J + 1; interior only
+    auto put = [&](int k, const T (&q)[2][2][NV]) {
+        T *row0 = u + (int64_t)k * su + (int64_t)(2 * J) * pu;
+        if (J >= 1) {
+            store_n<T, VEC, NV>(row0, f0, 1, w - 2, q[0][0]);
+            store_n<T, VEC, NV>(row0, f0 + NV, 1, w - 2, q[0][1]);
+        }
+        store_n<T, VEC, NV>(row0 + pu, f0, 1, w - 2, q[1][0]);
+        store_n<T, VEC, NV>(row0 + pu, f0 + NV, 1, w - 2, q[1][1]);
+    };
+    // one step of the march: a, b, c hold the coarse planes K - 1 (plane -1: the
+    // slot starts as plane 3), K and K + 1; d receives plane K + 2 (plane dc: the
+    // slot starts as plane dc - 4). The four sets rotate by name, not by copies
+    auto step = [&](int K, T (&a)[2][2][NV], const T (&b)[2][2][NV], const T (&cc)[2][2][NV], T (&d)[2][2][NV]) {
+        T mid[2][2][NV];
+        plane(K + 2 == dc ? max(dc - 4, 0) : K + 2, d);
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int v = 0; v < 2; ++v)
+#pragma unroll
+                for (int e = 0; e < NV; ++e) {
+                    if (K == 0) a[r][v][e] = cubic_ghost<T>(dcubic, b[r][v][e], cc[r][v][e], d[r][v][e], a[r][v][e]);
+                    if (K + 2 == dc) d[r][v][e] = cubic_ghost<T>(dcubic, cc[r][v][e], b[r][v][e], a[r][v][e], d[r][v][e]);
+                    mid[r][v][e] = cubic_mid<T>(a[r][v][e], b[r][v][e], cc[r][v][e], d[r][v][e]);
+                }
+        if (K >= 1) put(2 * K, b);  // fine plane 0 is boundary
+        put(2 * K + 1, mid);
+    };
+    T q0[2][2][NV], q1[2][2][NV], q2[2][2][NV], q3[2][2][NV];
+    plane(K0 == 0 ? min(3, dc - 1) : K0 - 1, q0);
+    plane(K0, q1);
+    plane(K0 + 1, q2);
+    for (int K = K0; K < K1; K += 4) {
+        step(K, q0, q1, q2, q3);
+        if (K + 1 >= K1) break;
+        step(K + 1, q1, q2, q3, q0);
+        if (K + 2 >= K1) break;
+        step(K + 2, q2, q3, q0, q1);
+        if (K + 3 >= K1) break;
+        step(K + 3, q3, q0, q1, q2);
+    }
+}
+
 inline bool mg3_strides_ok(int h, int w, int pitch, int64_t plane) {
     return pitch >= w && plane >= (int64_t)h * pitch;
 }
@@ -445,6 +628,31 @@ int launch_mg3_transfer(const T *coarse_or_r, T *out, int dc, int hc, int wc, in
     return MPX_OK;
 }
 
+// the cubic prolongation: one wave per coarse row 0 .. hc - 2 and block of the coarse planes 0 .. dc - 2
+template <typename T>
+int launch_mg3_prolong_cubic(const T *c, T *u, int dc, int hc, int wc, int pc, int64_t sc, int pu, int64_t su,
+                             void *stream) {
+    MPX_CHECK_ARG(c && u, "null pointer");
+    MPX_CHECK_ARG(mg3_coarse_ok(dc, hc, wc) && dc >= 3 && hc >= 3 && wc >= 3, "bad grid geometry");
+    MPX_CHECK_ARG(mg3_strides_ok(2 * hc - 1, 2 * wc - 1, pu, su) && mg3_strides_ok(hc, wc, pc, sc),
+                  "bad strides (pitch >= W, plane stride >= H * pitch)");
+    const bool vec = mg3_vec<T>({c, u}, {pc, pu}, {sc, su});
+    const int lanes = vec ? (wc + JVec<T>::n - 1) / JVec<T>::n : wc;
+    const int nxb = (lanes + 63) / 64;
+    const int kpl = mg3_walk((int64_t)nxb * (hc - 1), dc - 1, mg3_cubic_planes());
+    const int njb = (hc - 1 + kMg3Waves - 1) / kMg3Waves;
+    const int64_t nblk = (int64_t)nxb * njb * ((dc - 1 + kpl - 1) / kpl);
+    MPX_CHECK_ARG(nblk <= INT_MAX, "grid too large for one launch");
+    const dim3 blk(64, kMg3Waves), grd((unsigned)nblk);
+    hipStream_t s = as_stream(stream);
+    if (vec) hipLaunchKernelGGL((mg3_prolong_cubic_kernel<T, true>), grd, blk, 0, s, c, u, dc, hc, wc, pc, sc, pu, su, nxb,
+                                njb, kpl);
+    else hipLaunchKernelGGL((mg3_prolong_cubic_kernel<T, false>), grd, blk, 0, s, c, u, dc, hc, wc, pc, sc, pu, su, nxb,
+                            njb, kpl);
+    MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
+    return MPX_OK;
+}
+
 }  // namespace
 MPX_MODULE_ANCHOR(multigrid3d)
 
@@ -496,6 +704,16 @@ extern "C" int mpx_mg3_prolong_add_f32(const float *e, float *u, int dc, int hc,
     return mpx::launch_mg3_transfer<float, false>(e, u, dc, hc, wc, pitch_u, plane_u, pitch_e, plane_e, stream);
 }
 
+extern "C" int mpx_mg3_prolong_cubic_f64(const double *c, double *u, int dc, int hc, int wc, int pitch_c, int64_t plane_c,
+                                         int pitch_u, int64_t plane_u, void *stream) {
+    return mpx::launch_mg3_prolong_cubic<double>(c, u, dc, hc, wc, pitch_c, plane_c, pitch_u, plane_u, stream);
+}
+
+extern "C" int mpx_mg3_prolong_cubic_f32(const float *c, float *u, int dc, int hc, int wc, int pitch_c, int64_t plane_c,
+                                         int pitch_u, int64_t plane_u, void *stream) {
+    return mpx::launch_mg3_prolong_cubic<float>(c, u, dc, hc, wc, pitch_c, plane_c, pitch_u, plane_u, stream);
+}
+
 extern "C" int mpx_mg3_walk(int *out) {
     MPX_CHECK_ARG(out, "null out");
     const mpx::Mg3Walk &w = mpx::mg3_walk_config();
@@ -504,5 +722,13 @@ extern "C" int mpx_mg3_walk(int *out) {
     out[2] = w.prolong_planes;
     out[3] = w.min_waves;
     out[4] = mpx::kMg3Waves;
+    return MPX_OK;
+}
+
+extern "C" int mpx_mg3_cubic_walk(int *out) {
+    MPX_CHECK_ARG(out, "null out");
+    out[0] = mpx::mg3_cubic_planes();
+    out[1] = mpx::mg3_walk_config().min_waves;
+    out[2] = mpx::kMg3Waves;
     return MPX_OK;
 }

@@ -6,23 +6,30 @@ SlabJacobi3D solve of the same problem in the same session.
 
   python tools/bench_multigrid3d.py [--planes 255] [--ny 257] [--nx 257] [--fp32]
                                     [--tol 1e-8] [--reps 20] [--no-solve] [--no-kernels]
-                                    [--tail-points N] [--tail-table]
+                                    [--tail-points N] [--tail-table] [--fmg]
 
 Per-kernel times: device events around single launches, median over --reps
 launches that rotate through buffer sets larger than the 256 MiB Infinity
 Cache together, so no launch finds its input cached. The rates count the words
 the algorithm needs per fine point: relax 3, residual 3, restrict 1 + 1/8,
-prolong-add 2 + 1/8. ``rhs_sweep_even`` is ops.jacobi3d_sweep(rhs=) on the
+prolong-add 2 + 1/8, prolong_cubic 1 + 1/8. ``rhs_sweep_even`` is ops.jacobi3d_sweep(rhs=) on the
 contiguous (planes + 1, ny - 1, nx - 1) grid, whose even width takes the
 wave-strip kernel: the yardstick for ``relax``. ``below_level2_share`` is the
 time of the sub-cycle from level 2 down over the whole cycle. ``walk`` is
 ops.mg3_walk() (MPX_MG3_WALK="rows,restrict_planes,prolong_planes,min_waves"
-replaces it for A/B runs).
+replaces it for A/B runs); ``cubic_walk`` is ops.mg3_cubic_walk()
+(MPX_MG3_CUBIC_WALK="planes").
 
 ``--tail-points N``: the levels of at most N points run as one kernel (0: every
 level launched; default: the model's measured threshold); the JSON line carries
 ``tail_points``, ``tail_level`` and ``launches_per_cycle``. ``--tail-table``: per
 level, the sub-cycle from that level down, launched and fused (``tail_table``).
+
+``--fmg``: full multigrid (``fmg()``, two cycles per level, and ``fmg(1)``) on
+the manufactured problem u = sin(3x + 0.4) e^y cos(2z), b = 12 h^2 u, next to
+``solve(tol)`` from a zero interior and ``cycle()`` in the same process (key
+``fmg``): times, rho = max|u_fmg - u_h| / max|u_h - u| with u_h the fp64 model
+cycled 30 times, the error against u, and the launches of one ``fmg()``.
 
 Prints one JSON line.
 """
@@ -90,6 +97,8 @@ def kernel_times(planes, ny, nx, dt, reps, dev):
         c = [s._lv[1] for s in sets]
         out["restrict"] = (median_us(lambda k: ops.mg3_restrict(f[k].r, c[k].b), nsets, reps, dev), 1.125)
         out["prolong_add"] = (median_us(lambda k: ops.mg3_prolong_add_(c[k].u, f[k].u), nsets, reps, dev), 2.125)
+        if min(shapes[1]) >= 3:
+            out["prolong_cubic"] = (median_us(lambda k: ops.mg3_prolong_cubic(c[k].u, f[k].u), nsets, reps, dev), 1.125)
     del sets, f
     de, he, we = d - 1, h - 1, w - 1  # the even box next to it: the wave-strip kernel
     ev = [[torch.rand((de, he, we), dtype=dt, device=dev) for _ in range(3)] for _ in range(nsets)]
@@ -137,6 +146,101 @@ def tail_table(planes, ny, nx, dt, reps, max_points, dev):
     return rows_out
 
 
+def manufactured(planes, ny, nx):
+    """u = sin(3x + 0.4) e^y cos(2z) on the grid of spacing h = 1 / (nx - 1), and h: -Laplace(u) = 12 u."""
+    h = 1.0 / (nx - 1)
+    z = torch.arange(planes + 2, dtype=torch.float64).view(-1, 1, 1) * h
+    y = torch.arange(ny, dtype=torch.float64).view(1, -1, 1) * h
+    x = torch.arange(nx, dtype=torch.float64).view(1, 1, -1) * h
+    return torch.sin(3.0 * x + 0.4) * torch.exp(y) * torch.cos(2.0 * z), h
+
+
+def fmg_launches(m, cpl):
+    """Launches of one fmg(cpl), counted as ``launches_per_cycle`` counts: a
+    fill or a copy is one launch, the zeroing of the residual word none."""
+    n, tail = len(m.levels), m.tail_level
+
+    def cycle_from(k):
+        if tail is not None and k >= tail:
+            return 1
+        bottom = 1 if tail is not None else (1 if m.levels[-1] == (3, 3, 3) else m.coarse_sweeps)
+        if k == n - 1:
+            return bottom if n > 1 else m.nu1 + m.nu2
+        launched = (n - 1 if tail is None else tail) - k
+        return launched * (m.nu1 + m.nu2 + 4) + bottom
+
+    total = (n - 1) + 2 + 5 * (n - 1) + 1  # restrictions of b, the injected faces, the coarsest interior
+    total += cpl * cycle_from(n - 1)
+    for k in range(n - 1):
+        total += 3 + cpl * cycle_from(k)  # the prolongation and the two fills of the coarser un
+    return total
+
+
+def fmg_report(planes, ny, nx, dt, reps, tol, tail_points, dev):
+    exact, h = manufactured(planes, ny, nx)
+    exact = exact.to(dev)
+    rhs = (12.0 * h * h * exact)[1:-1]
+
+    def problem(dtype):
+        m = PoissonMultigrid3D(planes, ny, nx, dtype=dtype, device=dev, tail_points=tail_points)
+        m.set_rhs(tensor=rhs)
+        m.u.copy_(exact)
+        m.u[1:-1, 1:-1, 1:-1] = 0.0
+        m._lv[0].un.copy_(m.u)
+        return m
+
+    def timed(fn, n):
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize(dev)
+            ts.append(time.perf_counter() - t0)
+        return statistics.median(ts) * 1e3
+
+    def err(m, ref):
+        return float((m.u.to(torch.float64) - ref).abs().max())
+
+    out = {}
+    m = problem(dt)
+    for _ in range(2):
+        m.fmg()
+    out["fmg_ms"] = round(timed(m.fmg, reps), 4)
+    ufmg = m.u.to(torch.float64).clone()
+    out["fmg_residual"] = m.last_residual
+    out["fmg_error"] = err(m, exact)
+    out["fmg_launches"] = fmg_launches(m, 2)
+    m.fmg(1)
+    out["fmg1_ms"] = round(timed(lambda: m.fmg(1), reps), 4)
+    ufmg1 = m.u.to(torch.float64).clone()
+    out["fmg1_error"] = err(m, exact)
+    out["fmg1_launches"] = fmg_launches(m, 1)
+    out["cycle_ms"] = round(timed(m.cycle, reps), 4)
+    out["launches_per_cycle"] = m.launches_per_cycle
+    del m
+    # solve(tol) from a zero interior: the second solve, on kernels and buffers already warm
+    for k in range(2):
+        s = problem(dt)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        n = s.solve(tol)
+        torch.cuda.synchronize(dev)
+        out.update({"solve_ms": round((time.perf_counter() - t0) * 1e3, 3), "solve_cycles": n,
+                    "solve_residual": s.last_residual, "solve_error": err(s, exact)})
+        del s
+    # the discrete solution in fp64, whatever the dtype timed
+    d = problem(torch.float64)
+    for _ in range(30):
+        d.cycle()
+    disc = err(d, exact)
+    out.update({"discretisation_error": disc, "uh_residual": d.last_residual,
+                "rho": round(float((ufmg - d.u).abs().max()) / disc, 4),
+                "rho1": round(float((ufmg1 - d.u).abs().max()) / disc, 4)})
+    out["fmg_over_cycle"] = round(out["fmg_ms"] / out["cycle_ms"], 3)
+    return out
+
+
 def main() -> int:
     p = argparse.ArgumentParser()
     p.add_argument("--planes", type=int, default=255)
@@ -153,6 +257,8 @@ def main() -> int:
                    help="time the sub-cycle from every level of at most --tail-table-max points down, launched and fused")
     p.add_argument("--tail-table-max", type=int, default=274625)
     p.add_argument("--no-cycle", action="store_true", help="skip the cycle time")
+    p.add_argument("--fmg", action="store_true",
+                   help="full multigrid on the manufactured problem next to solve(tol) and cycle() (key fmg)")
     p.add_argument("--max-jacobi-iters", type=int, default=100000)
     a = p.parse_args()
     if not torch.cuda.is_available():
@@ -220,13 +326,16 @@ def main() -> int:
         solve["jacobi_over_multigrid"] = round(solve["jacobi_solve_ms"] / solve["solve_ms"], 2)
         solve["max_abs_difference"] = float((s.u - j.u).abs().max())
 
+    fmg = fmg_report(planes, ny, nx, dt, a.reps, a.tol, a.tail_points, dev) if a.fmg else None
+
     print(json.dumps({
         "metric": "3-D Poisson multigrid V(2,2) cycle time on one MI355X",
         "value": None if cycle_ms is None else round(cycle_ms, 4), "unit": "ms/cycle", "higher_is_better": False,
         "grid": [planes + 2, ny, nx], "dtype": "fp32" if a.fp32 else "fp64", "levels": len(levels),
         "coarsest": list(levels[-1]), "reps": a.reps, "tol": a.tol, "walk": ops.mg3_walk(),
+        "cubic_walk": ops.mg3_cubic_walk(),
         "below_level2_share": None if share is None else round(share, 3),
-        **plan, "tail_table": table, "level0_kernels": kern, **solve}), flush=True)
+        **plan, "tail_table": table, "level0_kernels": kern, "fmg": fmg, **solve}), flush=True)
     return 0
 
 
