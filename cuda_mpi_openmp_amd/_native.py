@@ -178,7 +178,16 @@ _SIGNATURES = {
     "mpx_sort_pairs_workspace_bytes": (c_i64, [c_i64, c_int]),
     "mpx_sort_pairs_ws": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp]),
     "mpx_cpu_sort_pairs": (None, [c_vp, c_vp, c_i64, c_int, c_int]),
-    "mpx_rows_checksum": (c_int, [c_vp, c_i64, c_int, c_i64, c_int, c_vp, c_vp]),
+    # lab4 LU: factor (a, n, pitch, piv, info, ws, ws_bytes, stream),
+    # solve (lu, n, pitch, piv, b, nrhs, pitch_b, ws, ws_bytes, stream), phase (..., info, j0, phase, ws, ...)
+    "mpx_lu_workspace_bytes": (c_i64, [c_int]),
+    "mpx_lu_panel_width": (c_int, []),
+    "mpx_lu_factor_f64": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "mpx_lu_solve_f64": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_int, c_i64, c_vp, c_i64, c_vp]),
+    "mpx_lu_phase_f64": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_int, c_int, c_vp, c_i64, c_vp]),
+    "mpx_cpu_lu_factor_f64": (None, [c_vp, c_int, c_i64, c_vp, c_vp]),
+    "mpx_cpu_lu_solve_f64": (None, [c_vp, c_int, c_i64, c_vp, c_vp, c_int, c_i64]),
+    "mpx_rows_checksum":(c_int, [c_vp, c_i64, c_int, c_i64, c_int, c_vp, c_vp]),
     "mpx_peer_probe_run": (c_int, [c_vp, c_vp]),
     "mpx_halo_fetch_run": (c_int, [c_vp, c_vp]),
     "mpx_conv_stream_peer_ok": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),

@@ -1,9 +1,10 @@
-"""The four workloads ("model families") of the suite, each with a single-device
+"""The workloads ("model families") of the suite, each with a single-device
 form and a row/shard-decomposed multi-GPU form:
 
   lab1  VectorSub / ShardedVectorSub           element-wise fp64/fp32 c = a - b
   lab2  EdgeDetector / SlabEdgeDetector        Roberts cross + KxK convolutions
   lab3  PixelClassifier / SlabPixelClassifier  Mahalanobis ML classification
+  lab4  DenseLU                                dense fp64 LU: solve, log-determinant, inverse (one device)
   stencil  SlabJacobi                          2-D Jacobi with halo exchange
   stencil  SlabJacobi3D                        3-D Jacobi on plane slabs
   stencil  PoissonMultigrid                    2-D Poisson by geometric multigrid V-cycles (one device)
@@ -11,6 +12,7 @@ form and a row/shard-decomposed multi-GPU form:
 """
 
 from .classifier import PixelClassifier, SlabPixelClassifier
+from .dense import DenseLU
 from .edge import EdgeDetector, SlabEdgeDetector
 from .jacobi import SlabJacobi
 from .jacobi3d import SlabJacobi3D
@@ -19,4 +21,4 @@ from .multigrid3d import PoissonMultigrid3D
 from .vector import ShardedVectorSub, VectorSub
 
 __all__ = ["PixelClassifier", "SlabPixelClassifier", "EdgeDetector", "SlabEdgeDetector", "SlabJacobi", "SlabJacobi3D",
-           "PoissonMultigrid", "PoissonMultigrid3D", "ShardedVectorSub", "VectorSub"]
+           "PoissonMultigrid", "PoissonMultigrid3D", "ShardedVectorSub", "VectorSub", "DenseLU"]

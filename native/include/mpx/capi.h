@@ -615,6 +615,52 @@ int64_t mpx_sort_pairs_workspace_bytes(int64_t n, int dtype);
 int mpx_sort_pairs_ws(void *keys, uint32_t *vals, int64_t n, int dtype, int flags, void *workspace,
                       int64_t workspace_bytes, void *stream);
 
+/* ---------------- lab4: dense LU with partial pivoting, fp64 (no reference program) ---------------- */
+/* Right-looking LU of a square row-major n x n matrix, in place
+ * (native/src/kernels/lu.hip): unit-lower L (multipliers a_ik / pivot below the
+ * diagonal) and U (on and above it) in one array, as LAPACK getrf stores them.
+ * Column k's pivot is the row i >= k of largest |a_ik| in the updated column,
+ * the lowest row index among equal magnitudes; piv[k] is that row (0-based: the
+ * row interchanged with row k, LAPACK's ipiv minus one), and the interchange
+ * moves the whole row. A column whose remaining part is exactly zero takes
+ * piv[k] = k, is left as it is, and elimination goes on; *info (a device word)
+ * receives k + 1 for the first such k and 0 otherwise. NaN / inf propagate and
+ * the pivots chosen among them are unspecified.
+ * Panels of 64 columns: one launch per panel column while more than 256 rows
+ * remain (partial pivot searches folded by the last workgroup to finish, found
+ * with a counter, never by waiting), one workgroup for the rest; row
+ * interchanges outside the panel, U12 by substitution with the panel's unit
+ * triangle, and the trailing update on v_mfma_f64_16x16x4_f64. The MFMA's
+ * accumulation order is unspecified, so the GPU and the CPU reference do not
+ * agree bit for bit on general input; both satisfy the componentwise backward
+ * error bounds of LU (tests/test_lu.py) and agree exactly wherever every
+ * intermediate is exactly representable.
+ * solve: B (n x nrhs, row-major, pitch_b) <- A^-1 B with the factors: rows
+ * interchanged by piv, then forward substitution with unit L and back
+ * substitution with U in blocks of 64 rows, the diagonal blocks by substitution
+ * (never an inverse), the blocks between them by the MFMA update.
+ * pitch >= n and pitch_b >= nrhs are row pitches in elements; padding is never
+ * read or written; 16-byte aligned bases with even pitches load the update's
+ * operands 16 bytes at a time, everything else 8. The workspace is the
+ * caller's, >= mpx_lu_workspace_bytes(n) bytes, 16-byte aligned and
+ * stream-ordered (mpx_sort_ws's rule); the solve needs none and ignores it.
+ * MPX_ERR_ARG before any pointer is touched: n < 0, nrhs < 0, pitch < n,
+ * pitch_b < nrhs, a null pointer, a short workspace. n = 0 and nrhs = 0 are
+ * no-ops. No allocation, no synchronisation. */
+int64_t mpx_lu_workspace_bytes(int n);
+int mpx_lu_factor_f64(double *a, int n, int64_t pitch, int32_t *piv, int32_t *info, void *workspace,
+                      int64_t workspace_bytes, void *stream);
+int mpx_lu_solve_f64(const double *lu, int n, int64_t pitch, const int32_t *piv, double *b, int nrhs,
+                     int64_t pitch_b, void *workspace, int64_t workspace_bytes, void *stream);
+/* Tuning-harness entries (tools/bench_lu.py): the phases of one panel step at
+ * column j0 (a multiple of the panel width with more than 256 rows left) on their own. phase 0: the panel
+ * (needs the workspace), 1: the interchanges outside it, 2: U12, 3: the
+ * trailing update. mpx_lu_panel_width: the panel width in use, 64, or
+ * MPX_LU_NB = 16 / 32 from the environment (the sweep; read once per process). */
+int mpx_lu_panel_width(void);
+int mpx_lu_phase_f64(double *a, int n, int64_t pitch, int32_t *piv, int32_t *info, int j0, int phase,
+                     void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---------------- CPU references (OpenMP, -O3, same numerics) ---------------- */
 int mpx_cpu_threads(void);
 void mpx_cpu_vsub_f64(const double *a, const double *b, double *c, int64_t n);
@@ -665,6 +711,11 @@ int mpx_cpu_mg3_prolong_add_f64(const double *e, double *u, int dc, int hc, int 
                                 int pitch_u, int64_t plane_u);
 void mpx_cpu_sort(void *data, int64_t n, int dtype);
 void mpx_cpu_sort_pairs(void *keys, uint32_t *vals, int64_t n, int dtype, int flags);
+/* the unblocked algorithm of mpx_lu_factor_f64 / mpx_lu_solve_f64 (info: a host
+ * word); bad arguments write nothing but *info = 0 */
+void mpx_cpu_lu_factor_f64(double *a, int n, int64_t pitch, int32_t *piv, int32_t *info);
+void mpx_cpu_lu_solve_f64(const double *lu, int n, int64_t pitch, const int32_t *piv, double *b, int nrhs,
+                          int64_t pitch_b);
 
 #ifdef __cplusplus
 }

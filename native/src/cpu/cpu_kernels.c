@@ -1126,3 +1126,83 @@ void mpx_cpu_sort_pairs(void *keys, uint32_t *vals, int64_t n, int dtype, int fl
     free(tmp);
     free(pay);
 }
+
+/* ---- lab4: dense LU with partial pivoting (the contract is in capi.h) ---- */
+void mpx_cpu_lu_factor_f64(double *a, int n, int64_t pitch, int32_t *piv, int32_t *info) {
+    if (info) *info = 0;
+    if (!a || !piv || n <= 0 || pitch < n) return;
+    for (int k = 0; k < n; ++k) {
+        int p = k;
+        double best = fabs(a[k * pitch + k]);
+        for (int i = k + 1; i < n; ++i) {
+            const double v = fabs(a[i * pitch + k]);
+            if (v > best) { /* strict: the lowest row wins among equal magnitudes */
+                best = v;
+                p = i;
+            }
+        }
+        if (best == 0.0) {
+            piv[k] = k;
+            if (info && *info == 0) *info = k + 1;
+            continue;
+        }
+        piv[k] = p;
+        double *rk = a + k * pitch;
+        if (p != k) {
+            double *rp = a + p * pitch;
+            for (int j = 0; j < n; ++j) {
+                const double t = rk[j];
+                rk[j] = rp[j];
+                rp[j] = t;
+            }
+        }
+        const double d = rk[k];
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static) if ((int64_t)(n - k) * (n - k) > 16384)
+#endif
+        for (int i = k + 1; i < n; ++i) {
+            double *ri = a + i * pitch;
+            const double l = ri[k] / d;
+            ri[k] = l;
+            for (int j = k + 1; j < n; ++j) ri[j] -= l * rk[j];
+        }
+    }
+}
+
+void mpx_cpu_lu_solve_f64(const double *lu, int n, int64_t pitch, const int32_t *piv, double *b, int nrhs,
+                          int64_t pitch_b) {
+    if (!lu || !piv || !b || n <= 0 || nrhs <= 0 || pitch < n || pitch_b < nrhs) return;
+    for (int k = 0; k < n; ++k) {
+        const int p = piv[k];
+        if (p == k) continue;
+        for (int j = 0; j < nrhs; ++j) {
+            const double t = b[k * pitch_b + j];
+            b[k * pitch_b + j] = b[p * pitch_b + j];
+            b[p * pitch_b + j] = t;
+        }
+    }
+    /* forward with unit L, then back with U: row i takes the finished rows k */
+    for (int i = 1; i < n; ++i) {
+        double *bi = b + i * pitch_b;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static) if ((int64_t)i * nrhs > 16384)
+#endif
+        for (int j = 0; j < nrhs; ++j) {
+            double s = bi[j];
+            for (int k = 0; k < i; ++k) s -= lu[i * pitch + k] * b[k * pitch_b + j];
+            bi[j] = s;
+        }
+    }
+    for (int i = n - 1; i >= 0; --i) {
+        double *bi = b + i * pitch_b;
+        const double d = lu[i * pitch + i];
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static) if ((int64_t)(n - i) * nrhs > 16384)
+#endif
+        for (int j = 0; j < nrhs; ++j) {
+            double s = bi[j];
+            for (int k = i + 1; k < n; ++k) s -= lu[i * pitch + k] * b[k * pitch_b + j];
+            bi[j] = s / d;
+        }
+    }
+}

@@ -38,6 +38,12 @@ void mpx_cpu_sort(void *data, int64_t n, int dtype);
 /* Stable key-value sort, same order and flags as mpx_sort_pairs_ws (capi.h:
  * 1 = MPX_SORT_IOTA, 2 = MPX_SORT_DESCENDING); int32 / float32 keys, n < 2^32. */
 void mpx_cpu_sort_pairs(void *keys, uint32_t *vals, int64_t n, int dtype, int flags);
+/* lab4: unblocked LU with partial pivoting and the solve with its factors, the
+ * contract of mpx_lu_factor_f64 / mpx_lu_solve_f64 (capi.h); bad arguments
+ * write nothing but *info = 0. */
+void mpx_cpu_lu_factor_f64(double *a, int n, int64_t pitch, int32_t *piv, int32_t *info);
+void mpx_cpu_lu_solve_f64(const double *lu, int n, int64_t pitch, const int32_t *piv, double *b, int nrhs,
+                          int64_t pitch_b);
 
 /* lab1 host text I/O (reference lab1/src/main.cu:46-52 scanf per value,
  * :82-84 printf per value), parallel over OpenMP threads in the -fopenmp builds
