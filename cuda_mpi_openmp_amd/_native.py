@@ -187,6 +187,13 @@ _SIGNATURES = {
     "mpx_lu_phase_f64": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_int, c_int, c_vp, c_i64, c_vp]),
     "mpx_cpu_lu_factor_f64": (None, [c_vp, c_int, c_i64, c_vp, c_vp]),
     "mpx_cpu_lu_solve_f64": (None, [c_vp, c_int, c_i64, c_vp, c_vp, c_int, c_i64]),
+    # batched LU: factor (a, batch, n, pitch, stride, piv, info, ws, ws_bytes, stream),
+    # solve (lu, batch, n, pitch, stride, piv, b, nrhs, pitch_b, stride_b, stream)
+    "mpx_lu_batched_workspace_bytes": (c_i64, [c_int, c_int]),
+    "mpx_lu_factor_batched_f64": (c_int, [c_vp, c_int, c_int, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "mpx_lu_solve_batched_f64": (c_int, [c_vp, c_int, c_int, c_i64, c_i64, c_vp, c_vp, c_int, c_i64, c_i64, c_vp]),
+    "mpx_cpu_lu_factor_batched_f64": (None, [c_vp, c_int, c_int, c_i64, c_i64, c_vp, c_vp]),
+    "mpx_cpu_lu_solve_batched_f64": (None, [c_vp, c_int, c_int, c_i64, c_i64, c_vp, c_vp, c_int, c_i64, c_i64]),
     "mpx_rows_checksum":(c_int, [c_vp, c_i64, c_int, c_i64, c_int, c_vp, c_vp]),
     "mpx_peer_probe_run": (c_int, [c_vp, c_vp]),
     "mpx_halo_fetch_run": (c_int, [c_vp, c_vp]),

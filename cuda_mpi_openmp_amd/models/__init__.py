@@ -5,6 +5,7 @@ form and a row/shard-decomposed multi-GPU form:
   lab2  EdgeDetector / SlabEdgeDetector        Roberts cross + KxK convolutions
   lab3  PixelClassifier / SlabPixelClassifier  Mahalanobis ML classification
   lab4  DenseLU                                dense fp64 LU: solve, log-determinant, inverse (one device)
+  lab4  BatchedDenseLU                         the same for a batch of small matrices, one launch each way
   stencil  SlabJacobi                          2-D Jacobi with halo exchange
   stencil  SlabJacobi3D                        3-D Jacobi on plane slabs
   stencil  PoissonMultigrid                    2-D Poisson by geometric multigrid V-cycles (one device)
@@ -12,7 +13,7 @@ form and a row/shard-decomposed multi-GPU form:
 """
 
 from .classifier import PixelClassifier, SlabPixelClassifier
-from .dense import DenseLU
+from .dense import BatchedDenseLU, DenseLU
 from .edge import EdgeDetector, SlabEdgeDetector
 from .jacobi import SlabJacobi
 from .jacobi3d import SlabJacobi3D
@@ -21,4 +22,5 @@ from .multigrid3d import PoissonMultigrid3D
 from .vector import ShardedVectorSub, VectorSub
 
 __all__ = ["PixelClassifier", "SlabPixelClassifier", "EdgeDetector", "SlabEdgeDetector", "SlabJacobi", "SlabJacobi3D",
-           "PoissonMultigrid", "PoissonMultigrid3D", "ShardedVectorSub", "VectorSub", "DenseLU"]
+           "PoissonMultigrid", "PoissonMultigrid3D", "ShardedVectorSub", "VectorSub", "DenseLU",
+           "BatchedDenseLU"]

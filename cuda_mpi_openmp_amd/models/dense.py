@@ -4,6 +4,10 @@
 answers from the factors: ``solve(B)``, ``slogdet()`` and ``inverse()``, which
 solves against the identity. A singular matrix (an exactly zero pivot) raises
 ``RuntimeError`` at construction, the one host read.
+
+``BatchedDenseLU`` is the same for a batch ``(B, n, n)`` of small matrices: one
+launch factors them all, one launch solves (``ops.lu_factor_batched``); any
+singular member raises at construction, naming its batch index and column.
 """
 
 from __future__ import annotations
@@ -29,3 +33,23 @@ class DenseLU:
 
     def inverse(self) -> torch.Tensor:
         return ops.lu_solve_(self.lu, self.piv, torch.eye(self.n, dtype=torch.float64, device=self.lu.device))
+
+
+class BatchedDenseLU:
+    def __init__(self, a: torch.Tensor):
+        self.lu, self.piv, info = ops.lu_factor_batched(a)
+        for m, k in enumerate(info.tolist()):
+            if k:
+                raise RuntimeError(f"BatchedDenseLU: matrix {m} of the batch is singular "
+                                   f"(zero pivot in column {k - 1})")
+        self.batch, self.n = self.lu.shape[0], self.lu.shape[1]
+
+    def solve(self, b: torch.Tensor) -> torch.Tensor:
+        return ops.lu_solve_batched(self.lu, self.piv, b)
+
+    def slogdet(self):
+        return ops.slogdet_batched(self.lu, self.piv)
+
+    def inverse(self) -> torch.Tensor:
+        eye = torch.eye(self.n, dtype=torch.float64, device=self.lu.device)
+        return ops.lu_solve_batched_(self.lu, self.piv, eye.repeat(self.batch, 1, 1))

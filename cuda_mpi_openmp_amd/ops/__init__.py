@@ -5,7 +5,9 @@ from .classify import class_stats, classify_
 from .classify import plan as classify_plan
 from .edge import ConvLauncher, conv, conv_rows, roberts, roberts_rgb
 from .filters import Filter, get_filter, list_filters
-from .linalg import lu_factor, lu_factor_, lu_solve, lu_solve_, lu_unpack, slogdet, solve
+from .linalg import (lu_factor, lu_factor_, lu_factor_batched, lu_factor_batched_, lu_solve, lu_solve_,
+                     lu_solve_batched, lu_solve_batched_, lu_unpack, lu_unpack_batched, slogdet, slogdet_batched, solve,
+                     solve_batched)
 from .multigrid import (jacobi_relax, mg_prolong_add_, mg_prolong_cubic, mg_residual, mg_restrict, mg_tail,
                         tail_sweeps)
 from .multigrid3d import (jacobi3d_relax, mg3_cubic_walk, mg3_prolong_add_, mg3_prolong_cubic, mg3_residual, mg3_restrict,
@@ -55,5 +57,12 @@ __all__ = [
     "lu_unpack",
     "slogdet",
     "solve",
+    "lu_factor_batched",
+    "lu_factor_batched_",
+    "lu_solve_batched",
+    "lu_solve_batched_",
+    "lu_unpack_batched",
+    "slogdet_batched",
+    "solve_batched",
     "vsub",
 ]

@@ -8,7 +8,12 @@ GPU tensors run the gfx950 kernels (the trailing update on
 ``v_mfma_f64_16x16x4_f64``) on the tensor's current stream with scratch from
 torch's allocator; CPU tensors run the unblocked OpenMP reference. The MFMA's
 accumulation order is unspecified, so the two agree to the componentwise
-backward-error bounds of LU, not bit for bit (tests/test_lu.py)."""
+backward-error bounds of LU, not bit for bit (tests/test_lu.py).
+
+The ``*_batched`` functions take ``(B, n, n)``. For n <= 64 the whole batch is
+one launch of plain VALU kernels in the CPU reference's operation order
+(lu_batched.hip), and there GPU and CPU do agree bit for bit, matrix by matrix
+(tests/test_lu_batched.py); larger n loops over the single-matrix kernels."""
 
 from __future__ import annotations
 
@@ -165,3 +170,178 @@ def lu_unpack(lu: torch.Tensor, piv: torch.Tensor):
         perm[k], perm[p] = perm[p], perm[k]
     low = torch.tril(lu, -1) + torch.eye(n, dtype=lu.dtype, device=lu.device)
     return torch.tensor(perm, dtype=torch.int64, device=lu.device), low, torch.triu(lu)
+
+
+# ---------------------------------------------------------------- batched: (B, n, n)
+def _check_batch(a: torch.Tensor, what: str):
+    if not isinstance(a, torch.Tensor):
+        raise ValueError(f"{what} must be a tensor")
+    if a.dtype != torch.float64:
+        raise ValueError(f"{what} must be float64 (fp64 only), not {a.dtype}")
+    if a.dim() != 3:
+        raise ValueError(f"{what} must be 3-D (batch, n, n), not {a.dim()}-D")
+    batch, n = a.shape[0], a.shape[1]
+    if a.shape[2] != n:
+        raise ValueError(f"{what} must be a batch of square matrices, not {tuple(a.shape)}")
+    if n >= 2 ** 31 or batch >= 2 ** 31:
+        raise ValueError(f"{what} is too large")
+    if n > 1 and a.stride(2) != 1:
+        raise ValueError(f"{what} must have contiguous rows (stride(2) == 1)")
+    if n > 1 and a.stride(1) < n:
+        raise ValueError(f"{what} must have a row stride of at least n")
+    pitch = a.stride(1) if n > 1 else max(n, 1)
+    span = (n - 1) * pitch + n
+    if batch > 1 and n and a.stride(0) < span:
+        raise ValueError(f"{what} must have a batch stride of at least (n - 1) * stride(1) + n")
+    return batch, n, pitch, (a.stride(0) if batch > 1 else span)
+
+
+def _check_batch_piv(piv: torch.Tensor, lu: torch.Tensor, batch: int, n: int) -> None:
+    if (not isinstance(piv, torch.Tensor) or piv.dtype != torch.int32 or piv.dim() != 2
+            or tuple(piv.shape) != (batch, n)):
+        raise ValueError(f"piv must be an int32 tensor of shape ({batch}, {n})")
+    if not piv.is_contiguous():
+        raise ValueError("piv must be contiguous")
+    if piv.device != lu.device:
+        raise ValueError(f"LU is on {lu.device}, piv on {piv.device}")
+
+
+def lu_factor_batched_(a: torch.Tensor):
+    """LU with partial pivoting of every matrix of a float64 batch ``(B, n, n)``,
+    in place: per matrix exactly ``lu_factor_`` of the CPU reference (bit for
+    bit for n <= 64, where the whole batch is one launch; larger n loops over
+    ``lu_factor_``'s kernels). Rows must be contiguous; any row stride >= n and
+    any batch stride >= (n - 1) * stride(1) + n are honoured (a slice of a
+    larger buffer works, its padding is never touched). Returns
+    ``(a, piv (B, n) int32, info (B,) int32)``; ``info[m]`` is 0, or k + 1 for
+    matrix m's first exactly zero pivot. No host synchronisation."""
+    batch, n, pitch, stride = _check_batch(a, "A")
+    piv = torch.empty((batch, n), dtype=torch.int32, device=a.device)
+    if batch == 0 or n == 0:
+        return a, piv, torch.zeros(batch, dtype=torch.int32, device=a.device)
+    info = torch.empty(batch, dtype=torch.int32, device=a.device)
+    L = _native.lib()
+    if a.is_cuda:
+        nbytes = int(L.mpx_lu_batched_workspace_bytes(batch, n))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device) if nbytes else None
+        with torch.cuda.device(a.device):
+            _native.check(L.mpx_lu_factor_batched_f64(a.data_ptr(), batch, n, pitch, stride, piv.data_ptr(),
+                                                      info.data_ptr(), ws.data_ptr() if nbytes else None, nbytes,
+                                                      _native.stream_of(a)))
+    else:
+        L.mpx_cpu_lu_factor_batched_f64(a.data_ptr(), batch, n, pitch, stride, piv.data_ptr(), info.data_ptr())
+    return a, piv, info
+
+
+def lu_factor_batched(a: torch.Tensor):
+    """``lu_factor_batched_`` on a contiguous copy; ``a`` is left untouched."""
+    _check_batch(a, "A")
+    return lu_factor_batched_(a.clone(memory_format=torch.contiguous_format))
+
+
+def _check_solve_batched(lu: torch.Tensor, piv: torch.Tensor, b: torch.Tensor):
+    batch, n, pitch, stride = _check_batch(lu, "LU")
+    _check_batch_piv(piv, lu, batch, n)
+    if not isinstance(b, torch.Tensor) or b.dtype != torch.float64:
+        raise ValueError("B must be float64 (fp64 only)")
+    if b.dim() not in (2, 3):
+        raise ValueError(f"B must be (batch, n) or (batch, n, k), not {b.dim()}-D")
+    if b.shape[0] != batch or b.shape[1] != n:
+        raise ValueError(f"B must be ({batch}, {n}) or ({batch}, {n}, k), not {tuple(b.shape)}")
+    if b.device != lu.device:
+        raise ValueError(f"LU is on {lu.device}, B on {b.device}")
+    return batch, n, pitch, stride
+
+
+def lu_solve_batched_(lu: torch.Tensor, piv: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Solve A_m X_m = B_m in place in ``b`` ((B, n, k) or (B, n), float64) with
+    the factors of ``lu_factor_batched``: per matrix exactly ``lu_solve_`` of the
+    CPU reference (bit for bit for n <= 64, one launch). A 3-D ``b`` needs
+    contiguous rows; any row stride >= k and batch stride >= (n - 1) * stride(1)
+    + k are honoured. A 2-D ``b`` may have any positive element stride."""
+    batch, n, pitch, stride = _check_solve_batched(lu, piv, b)
+    if b.dim() == 2:
+        nrhs = 1
+        if n > 1 and b.stride(1) < 1:
+            raise ValueError("B must have a positive stride")
+        pitch_b = b.stride(1) if n > 1 else 1
+    else:
+        nrhs = b.shape[2]
+        if nrhs > 1 and b.stride(2) != 1:
+            raise ValueError("B must have contiguous rows (stride(2) == 1)")
+        if n > 1 and b.stride(1) < nrhs:
+            raise ValueError("B must have a row stride of at least its width")
+        pitch_b = b.stride(1) if n > 1 else max(nrhs, 1)
+    span_b = (n - 1) * pitch_b + nrhs
+    if batch > 1 and n and nrhs and b.stride(0) < span_b:
+        raise ValueError("B must have a batch stride of at least (n - 1) * stride(1) + k")
+    if batch == 0 or n == 0 or nrhs == 0:
+        return b
+    stride_b = b.stride(0) if batch > 1 else span_b
+    L = _native.lib()
+    if lu.is_cuda:
+        with torch.cuda.device(lu.device):
+            _native.check(L.mpx_lu_solve_batched_f64(lu.data_ptr(), batch, n, pitch, stride, piv.data_ptr(),
+                                                     b.data_ptr(), nrhs, pitch_b, stride_b, _native.stream_of(lu)))
+    else:
+        L.mpx_cpu_lu_solve_batched_f64(lu.data_ptr(), batch, n, pitch, stride, piv.data_ptr(), b.data_ptr(), nrhs,
+                                       pitch_b, stride_b)
+    return b
+
+
+def lu_solve_batched(lu: torch.Tensor, piv: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """``lu_solve_batched_`` on a contiguous copy of ``b``."""
+    _check_solve_batched(lu, piv, b)
+    return lu_solve_batched_(lu, piv, b.clone(memory_format=torch.contiguous_format))
+
+
+def _raise_if_singular(info: torch.Tensor, who: str) -> None:
+    """The one host read: the first singular member of the batch and its column."""
+    host = info.tolist()
+    for m, k in enumerate(host):
+        if k:
+            raise RuntimeError(f"{who}: matrix {m} of the batch is singular (zero pivot in column {k - 1})")
+
+
+def solve_batched(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """X with A_m X_m = B_m for every member: factor a copy of ``a``, read
+    ``info`` (the one host read), solve on a copy of ``b``. A singular member
+    raises ``RuntimeError`` naming the first such batch index and its column."""
+    batch, n, _, _ = _check_batch(a, "A")
+    if not isinstance(b, torch.Tensor) or b.dtype != torch.float64:
+        raise ValueError("B must be float64 (fp64 only)")
+    if b.dim() not in (2, 3) or b.shape[0] != batch or b.shape[1] != n:
+        raise ValueError(f"B must be ({batch}, {n}) or ({batch}, {n}, k), not {tuple(b.shape)}")
+    if b.device != a.device:
+        raise ValueError(f"A is on {a.device}, B on {b.device}")
+    lu, piv, info = lu_factor_batched(a)
+    _raise_if_singular(info, "solve_batched")
+    return lu_solve_batched(lu, piv, b)
+
+
+def slogdet_batched(lu: torch.Tensor, piv: torch.Tensor):
+    """``(sign (B,), logabsdet (B,))`` of the factored matrices: the diagonals
+    of U and the parity of the interchanges (float64, no host read)."""
+    batch, n, _, _ = _check_batch(lu, "LU")
+    _check_batch_piv(piv, lu, batch, n)
+    d = torch.diagonal(lu, dim1=1, dim2=2)
+    swaps = (piv != torch.arange(n, dtype=torch.int32, device=lu.device)).sum(dim=1)
+    sign = torch.sign(d).prod(dim=1) * (1 - 2 * (swaps % 2)).to(torch.float64)
+    return sign, torch.log(torch.abs(d)).sum(dim=1)
+
+
+def lu_unpack_batched(lu: torch.Tensor, piv: torch.Tensor):
+    """``(perm (B, n) int64, L, U)`` with ``A[m][perm[m]] = L[m] @ U[m]`` (reads
+    ``piv`` on the host)."""
+    batch, n, _, _ = _check_batch(lu, "LU")
+    _check_batch_piv(piv, lu, batch, n)
+    host = piv.cpu()
+    perm = torch.arange(n, dtype=torch.int64).repeat(batch, 1)
+    rows = torch.arange(batch)
+    for k in range(n):
+        p = host[:, k].long()
+        at_k, at_p = perm[rows, k].clone(), perm[rows, p].clone()
+        perm[rows, k] = at_p
+        perm[rows, p] = at_k
+    low = torch.tril(lu, -1) + torch.eye(n, dtype=lu.dtype, device=lu.device)
+    return perm.to(lu.device), low, torch.triu(lu)

@@ -661,6 +661,42 @@ int mpx_lu_panel_width(void);
 int mpx_lu_phase_f64(double *a, int n, int64_t pitch, int32_t *piv, int32_t *info, int j0, int phase,
                      void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Batched: `batch` square n x n matrices of one size (native/src/kernels/lu_batched.hip).
+ * Matrix m starts at a + m * stride, its rows are pitch >= n elements apart,
+ * and stride >= (n - 1) * pitch + n for batch > 1 (64-bit arithmetic); the
+ * padding between rows and between matrices is never read or written. piv is
+ * (batch, n) contiguous int32, 0-based; info is batch int32 device words, each
+ * 0 or k + 1 for that matrix's first exactly zero pivot. B's matrix m starts at
+ * b + m * stride_b, rows pitch_b >= nrhs apart, stride_b >= (n - 1) * pitch_b + nrhs.
+ * n <= 64: per matrix the result is exactly what mpx_cpu_lu_factor_f64 /
+ * mpx_cpu_lu_solve_f64 produce for that matrix alone, bit for bit: the same
+ * pivot rule (largest magnitude, the lowest current row among equals, piv[k] = k
+ * and the column left as it is on an exactly zero column; a NaN at row k stays
+ * the pivot, a NaN below it never becomes one), l = a_ik / d by IEEE division,
+ * a_ij = a_ij - l u_kj for k ascending with every operation rounded once (no
+ * FMA), forward substitution s -= lu_ik b_kj for k ascending, back substitution
+ * the same for k = i + 1 .. n - 1 ascending and then one division by the
+ * diagonal. The factorisation is one launch: a lane holds one row in registers
+ * (padded to 8 / 16 / 32 / 64 columns, 64 / padded width matrices per wave), the
+ * matrix is read and written once, piv and info are written by the kernel. The
+ * solve is one launch: a lane is one (matrix, right-hand side) pair,
+ * 64 / min(nrhs, 64) matrices per wave; out-of-range pivot entries are skipped.
+ * Neither needs a workspace: mpx_lu_batched_workspace_bytes is 0 for n <= 64.
+ * n > 64: correct, not fast. A loop over the matrices through
+ * mpx_lu_factor_f64 / mpx_lu_solve_f64 on the same stream, with one workspace
+ * of mpx_lu_workspace_bytes(n) bytes (16-byte aligned) reused across the
+ * stream-ordered matrices; the yardstick there is the single-matrix one (exact
+ * recovery and the backward-error bounds), not bits.
+ * MPX_ERR_ARG before any pointer is touched: batch < 0, n < 0, nrhs < 0,
+ * pitch < n, pitch_b < nrhs, a short stride, a null pointer, a short or
+ * misaligned workspace. batch = 0, n = 0 and nrhs = 0 are no-ops. No
+ * allocation, no host synchronisation, everything on the given stream. */
+int64_t mpx_lu_batched_workspace_bytes(int batch, int n);
+int mpx_lu_factor_batched_f64(double *a, int batch, int n, int64_t pitch, int64_t stride, int32_t *piv,
+                              int32_t *info, void *workspace, int64_t workspace_bytes, void *stream);
+int mpx_lu_solve_batched_f64(const double *lu, int batch, int n, int64_t pitch, int64_t stride, const int32_t *piv,
+                             double *b, int nrhs, int64_t pitch_b, int64_t stride_b, void *stream);
+
 /* ---------------- CPU references (OpenMP, -O3, same numerics) ---------------- */
 int mpx_cpu_threads(void);
 void mpx_cpu_vsub_f64(const double *a, const double *b, double *c, int64_t n);
@@ -716,6 +752,12 @@ void mpx_cpu_sort_pairs(void *keys, uint32_t *vals, int64_t n, int dtype, int fl
 void mpx_cpu_lu_factor_f64(double *a, int n, int64_t pitch, int32_t *piv, int32_t *info);
 void mpx_cpu_lu_solve_f64(const double *lu, int n, int64_t pitch, const int32_t *piv, double *b, int nrhs,
                           int64_t pitch_b);
+/* the batched entries' reference and what CPU tensors run: an OpenMP loop over
+ * the matrices that calls the two functions above (info: batch host words) */
+void mpx_cpu_lu_factor_batched_f64(double *a, int batch, int n, int64_t pitch, int64_t stride, int32_t *piv,
+                                   int32_t *info);
+void mpx_cpu_lu_solve_batched_f64(const double *lu, int batch, int n, int64_t pitch, int64_t stride,
+                                  const int32_t *piv, double *b, int nrhs, int64_t pitch_b, int64_t stride_b);
 
 #ifdef __cplusplus
 }

@@ -39,6 +39,7 @@ const void *module_anchor_multigrid();
 const void *module_anchor_multigrid3d();
 const void *module_anchor_mg_tail();
 const void *module_anchor_lu();
+const void *module_anchor_lu_batched();
 }  // namespace mpx
 
 extern "C" int mpx_preload_modules(void) {
@@ -47,7 +48,8 @@ extern "C" int mpx_preload_modules(void) {
                              mpx::module_anchor_edge_roberts(), mpx::module_anchor_sort(),
                              mpx::module_anchor_edge_stream(), mpx::module_anchor_jacobi3d(),
                              mpx::module_anchor_multigrid(),    mpx::module_anchor_multigrid3d(),
-                             mpx::module_anchor_mg_tail(),      mpx::module_anchor_lu()};
+                             mpx::module_anchor_mg_tail(),      mpx::module_anchor_lu(),
+                             mpx::module_anchor_lu_batched()};
     for (const void *k : anchors) {
         hipFuncAttributes attr;
         MPX_RETURN_IF_HIP_ERROR(hipFuncGetAttributes(&attr, k));

@@ -1206,3 +1206,24 @@ void mpx_cpu_lu_solve_f64(const double *lu, int n, int64_t pitch, const int32_t 
         }
     }
 }
+
+/* batched: every matrix on its own through the single-matrix functions above
+ * (their inner OpenMP regions run serially inside this one) */
+void mpx_cpu_lu_factor_batched_f64(double *a, int batch, int n, int64_t pitch, int64_t stride, int32_t *piv,
+                                   int32_t *info) {
+    if (!a || !piv || !info || batch <= 0 || n < 0 || pitch < n) return;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static)
+#endif
+    for (int m = 0; m < batch; ++m) mpx_cpu_lu_factor_f64(a + m * stride, n, pitch, piv + (int64_t)m * n, info + m);
+}
+
+void mpx_cpu_lu_solve_batched_f64(const double *lu, int batch, int n, int64_t pitch, int64_t stride,
+                                  const int32_t *piv, double *b, int nrhs, int64_t pitch_b, int64_t stride_b) {
+    if (!lu || !piv || !b || batch <= 0) return;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static)
+#endif
+    for (int m = 0; m < batch; ++m)
+        mpx_cpu_lu_solve_f64(lu + m * stride, n, pitch, piv + (int64_t)m * n, b + m * stride_b, nrhs, pitch_b);
+}

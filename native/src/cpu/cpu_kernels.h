@@ -44,6 +44,13 @@ void mpx_cpu_sort_pairs(void *keys, uint32_t *vals, int64_t n, int dtype, int fl
 void mpx_cpu_lu_factor_f64(double *a, int n, int64_t pitch, int32_t *piv, int32_t *info);
 void mpx_cpu_lu_solve_f64(const double *lu, int n, int64_t pitch, const int32_t *piv, double *b, int nrhs,
                           int64_t pitch_b);
+/* The same for `batch` matrices (matrix m at a + m * stride, piv (batch, n), one
+ * info word each; B's matrices stride_b apart): an OpenMP loop over the matrices
+ * that calls the two functions above, so every matrix gets exactly their result. */
+void mpx_cpu_lu_factor_batched_f64(double *a, int batch, int n, int64_t pitch, int64_t stride, int32_t *piv,
+                                   int32_t *info);
+void mpx_cpu_lu_solve_batched_f64(const double *lu, int batch, int n, int64_t pitch, int64_t stride,
+                                  const int32_t *piv, double *b, int nrhs, int64_t pitch_b, int64_t stride_b);
 
 /* lab1 host text I/O (reference lab1/src/main.cu:46-52 scanf per value,
  * :82-84 printf per value), parallel over OpenMP threads in the -fopenmp builds
