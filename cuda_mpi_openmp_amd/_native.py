@@ -194,6 +194,12 @@ _SIGNATURES = {
     "mpx_lu_solve_batched_f64": (c_int, [c_vp, c_int, c_int, c_i64, c_i64, c_vp, c_vp, c_int, c_i64, c_i64, c_vp]),
     "mpx_cpu_lu_factor_batched_f64": (None, [c_vp, c_int, c_int, c_i64, c_i64, c_vp, c_vp]),
     "mpx_cpu_lu_solve_batched_f64": (None, [c_vp, c_int, c_int, c_i64, c_i64, c_vp, c_vp, c_int, c_i64, c_i64]),
+    # lab4 Cholesky (chol.hip): lower storage, no pivots, no workspace
+    "mpx_chol_factor_f64": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp]),
+    "mpx_chol_solve_f64": (c_int, [c_vp, c_int, c_i64, c_vp, c_int, c_i64, c_vp]),
+    "mpx_chol_phase_f64": (c_int, [c_vp, c_int, c_i64, c_vp, c_int, c_int, c_vp]),
+    "mpx_cpu_chol_factor_f64": (None, [c_vp, c_int, c_i64, c_vp]),
+    "mpx_cpu_chol_solve_f64": (None, [c_vp, c_int, c_i64, c_vp, c_int, c_i64]),
     "mpx_rows_checksum":(c_int, [c_vp, c_i64, c_int, c_i64, c_int, c_vp, c_vp]),
     "mpx_peer_probe_run": (c_int, [c_vp, c_vp]),
     "mpx_halo_fetch_run": (c_int, [c_vp, c_vp]),

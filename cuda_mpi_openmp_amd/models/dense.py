@@ -8,6 +8,11 @@ solves against the identity. A singular matrix (an exactly zero pivot) raises
 ``BatchedDenseLU`` is the same for a batch ``(B, n, n)`` of small matrices: one
 launch factors them all, one launch solves (``ops.lu_factor_batched``); any
 singular member raises at construction, naming its batch index and column.
+
+``DenseCholesky`` is ``DenseLU`` for a symmetric positive definite matrix (its
+lower triangle is what counts): half the work and no pivot search
+(``ops.cholesky_factor``). A matrix that is not positive definite raises at
+construction, naming the column where the factorisation broke down.
 """
 
 from __future__ import annotations
@@ -53,3 +58,21 @@ class BatchedDenseLU:
     def inverse(self) -> torch.Tensor:
         eye = torch.eye(self.n, dtype=torch.float64, device=self.lu.device)
         return ops.lu_solve_batched_(self.lu, self.piv, eye.repeat(self.batch, 1, 1))
+
+
+class DenseCholesky:
+    def __init__(self, a: torch.Tensor):
+        self.l, info = ops.cholesky_factor(a)
+        k = int(info.item())
+        if k:
+            raise RuntimeError(f"DenseCholesky: the matrix is not positive definite (column {k - 1})")
+        self.n = self.l.shape[0]
+
+    def solve(self, b: torch.Tensor) -> torch.Tensor:
+        return ops.cholesky_solve(self.l, b)
+
+    def logdet(self) -> torch.Tensor:
+        return ops.logdet_spd(self.l)
+
+    def inverse(self) -> torch.Tensor:
+        return ops.cholesky_solve_(self.l, torch.eye(self.n, dtype=torch.float64, device=self.l.device))

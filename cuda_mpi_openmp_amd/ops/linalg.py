@@ -1,5 +1,7 @@
 """lab4 operators: dense LU with partial pivoting in fp64 and what follows from
-its factors (solve, log-determinant, unpacking). The matrix lab has no reference
+its factors (solve, log-determinant, unpacking), and at the end of the file the
+Cholesky factorisation of symmetric positive definite matrices (``cholesky_*``,
+``solve_spd``, ``logdet_spd``; the contract is capi.h's ``mpx_chol_factor_f64``). The matrix lab has no reference
 program, so the contract is this package's (capi.h, ``mpx_lu_factor_f64``):
 LAPACK ``getrf`` storage, 0-based int32 pivots, the lowest row among equal
 magnitudes, ``info = k + 1`` for the first exactly zero pivot.
@@ -345,3 +347,112 @@ def lu_unpack_batched(lu: torch.Tensor, piv: torch.Tensor):
         perm[rows, p] = at_k
     low = torch.tril(lu, -1) + torch.eye(n, dtype=lu.dtype, device=lu.device)
     return perm.to(lu.device), low, torch.triu(lu)
+
+
+# ---------------------------------------------------------------- Cholesky: SPD, lower storage
+def cholesky_factor_(a: torch.Tensor):
+    """Cholesky factorisation A = L Lᵀ of a symmetric positive definite float64
+    matrix, in place, lower storage: only the lower triangle of ``a`` (diagonal
+    included) is read, and it holds L on return; the strict upper triangle and
+    any pitch padding are never read or written. Rows must be contiguous; any
+    row stride >= n is the pitch. Returns ``(a, info)``; ``info`` is a
+    one-element int32 tensor on ``a``'s device: 0, or j + 1 for the first column
+    whose reduced diagonal is not > 0 (zero, negative or NaN: not positive
+    definite). Columns before it are valid factor columns, the rest is
+    unspecified. GPU tensors run chol.hip on the current stream (two launches
+    per 64 columns, the update on ``v_mfma_f64_16x16x4_f64``), CPU tensors the
+    unblocked reference; columns 0..63 agree bit for bit, the rest to Cholesky's
+    backward-error bounds (tests/test_cholesky.py). No host synchronisation."""
+    n = _check_matrix(a, "A")
+    if n == 0:
+        return a, torch.zeros(1, dtype=torch.int32, device=a.device)
+    info = torch.empty(1, dtype=torch.int32, device=a.device)
+    L = _native.lib()
+    if a.is_cuda:
+        with torch.cuda.device(a.device):
+            _native.check(L.mpx_chol_factor_f64(a.data_ptr(), n, _pitch(a, n), info.data_ptr(), _native.stream_of(a)))
+    else:
+        L.mpx_cpu_chol_factor_f64(a.data_ptr(), n, _pitch(a, n), info.data_ptr())
+    return a, info
+
+
+def cholesky_factor(a: torch.Tensor):
+    """``cholesky_factor_`` on a contiguous copy; ``a`` is left untouched (the
+    copy's upper triangle is ``a``'s)."""
+    _check_matrix(a, "A")
+    return cholesky_factor_(a.clone(memory_format=torch.contiguous_format))
+
+
+def _check_cholesky_solve(l: torch.Tensor, b: torch.Tensor) -> int:
+    n = _check_matrix(l, "L")
+    if not isinstance(b, torch.Tensor) or b.dtype != torch.float64:
+        raise ValueError("B must be float64 (fp64 only)")
+    if b.dim() not in (1, 2):
+        raise ValueError(f"B must be (n,) or (n, k), not {b.dim()}-D")
+    if b.shape[0] != n:
+        raise ValueError(f"B has {b.shape[0]} rows, L {n}")
+    if b.device != l.device:
+        raise ValueError(f"L is on {l.device}, B on {b.device}")
+    return n
+
+
+def cholesky_solve_(l: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Solve A X = B in place in ``b`` ((n,) or (n, k), float64) with the factor
+    of ``cholesky_factor``: forward substitution with L, back substitution with
+    Lᵀ, both dividing by the diagonal; only L's lower triangle is read. ``b``
+    has ``lu_solve_``'s stride rules: a 2-D ``b`` needs contiguous rows (any row
+    stride >= k is the pitch), a 1-D ``b`` may have any positive stride."""
+    n = _check_cholesky_solve(l, b)
+    if b.dim() == 1:
+        nrhs, pitch_b = 1, (max(b.stride(0), 1) if n > 1 else 1)
+        if n > 1 and b.stride(0) < 1:
+            raise ValueError("B must have a positive stride")
+    else:
+        nrhs = b.shape[1]
+        if nrhs and b.stride(1) != 1:
+            raise ValueError("B must have contiguous rows (stride(1) == 1)")
+        if n > 1 and b.stride(0) < nrhs:
+            raise ValueError("B must have a row stride of at least its width")
+        pitch_b = _pitch(b, nrhs)
+    if n == 0 or nrhs == 0:
+        return b
+    L = _native.lib()
+    if l.is_cuda:
+        with torch.cuda.device(l.device):
+            _native.check(L.mpx_chol_solve_f64(l.data_ptr(), n, _pitch(l, n), b.data_ptr(), nrhs, pitch_b,
+                                               _native.stream_of(l)))
+    else:
+        L.mpx_cpu_chol_solve_f64(l.data_ptr(), n, _pitch(l, n), b.data_ptr(), nrhs, pitch_b)
+    return b
+
+
+def cholesky_solve(l: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """``cholesky_solve_`` on a contiguous copy of ``b``."""
+    _check_cholesky_solve(l, b)
+    return cholesky_solve_(l, b.clone(memory_format=torch.contiguous_format))
+
+
+def solve_spd(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """X with A X = B for a symmetric positive definite A (its lower triangle is
+    what counts): factor a copy of ``a``, read ``info`` (the one host read),
+    solve on a copy of ``b``. A matrix that is not positive definite raises
+    ``RuntimeError`` naming the column where the factorisation broke down."""
+    n = _check_matrix(a, "A")
+    if not isinstance(b, torch.Tensor) or b.dtype != torch.float64:
+        raise ValueError("B must be float64 (fp64 only)")
+    if b.dim() not in (1, 2) or b.shape[0] != n:
+        raise ValueError(f"B must be ({n},) or ({n}, k), not {tuple(b.shape)}")
+    if b.device != a.device:
+        raise ValueError(f"A is on {a.device}, B on {b.device}")
+    l, info = cholesky_factor(a)
+    k = int(info.item())
+    if k:
+        raise RuntimeError(f"solve_spd: the matrix is not positive definite (column {k - 1})")
+    return cholesky_solve(l, b)
+
+
+def logdet_spd(l: torch.Tensor) -> torch.Tensor:
+    """log det A = 2 Σ log l_ii from the factor of ``cholesky_factor`` (a 0-dim
+    float64 tensor, no host read)."""
+    _check_matrix(l, "L")
+    return 2.0 * torch.log(torch.diagonal(l)).sum()

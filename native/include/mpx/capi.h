@@ -697,6 +697,47 @@ int mpx_lu_factor_batched_f64(double *a, int batch, int n, int64_t pitch, int64_
 int mpx_lu_solve_batched_f64(const double *lu, int batch, int n, int64_t pitch, int64_t stride, const int32_t *piv,
                              double *b, int nrhs, int64_t pitch_b, int64_t stride_b, void *stream);
 
+/* lab4: Cholesky factorisation A = L L^T of a symmetric positive definite
+ * n x n fp64 matrix, row-major, lower storage, in place
+ * (native/src/kernels/chol.hip). Only the lower triangle (diagonal included) is
+ * read, and on exit it holds L; the strict upper triangle and the pitch padding
+ * are never read and never written. Per element, every operation rounded once
+ * (no FMA):
+ *   t = a_ij;  for k = 0 .. j-1 ascending:  t = t - (l_ik * l_jk)
+ *   j == i:  l_jj = sqrt(t)  (correctly rounded);   j < i:  l_ij = t / l_jj  (IEEE division)
+ * *info (a device word) is 0, or j + 1 for the first column whose reduced
+ * diagonal t is not > 0 (zero, negative and NaN alike). Columns 0 .. j-1 of L
+ * are then valid in every row, the rest of the lower triangle is unspecified;
+ * the kernels run on with whatever values result, and the first failure stays.
+ * Panels of 64 columns and nothing per column: one workgroup factors the
+ * diagonal block in LDS, L21 = A21 L11^-T by substitution with one lane per row,
+ * and A22 -= L21 L21^T on v_mfma_f64_16x16x4_f64 over the lower tiles only. The
+ * workgroup that updates the next diagonal block factors it on the spot, so a
+ * factorisation is 1 + 2 (ceil(n / 64) - 1) launches. The diagonal block and the
+ * panel solve are plain VALU in the order above, so columns 0 .. 63 of L (the
+ * whole factor for n <= 64) equal mpx_cpu_chol_factor_f64's bit for bit; from
+ * column 64 on the MFMA's unspecified accumulation order is in every element,
+ * and the yardsticks are exact recovery and the backward-error bounds
+ * (tests/test_cholesky.py).
+ * solve: B (n x nrhs, row-major, pitch_b) <- A^-1 B with L:
+ *   acc = b_i;  for k = 0 .. i-1 ascending:    acc -= l_ik y_k;   y_i = acc / l_ii
+ *   acc = y_i;  for k = i+1 .. n-1 ascending:  acc -= l_ki x_k;   x_i = acc / l_ii
+ * in blocks of 64 rows, the diagonal blocks by substitution (never an inverse),
+ * the blocks between them by the MFMA update (bit for bit the CPU reference's
+ * result for n <= 64). 16-byte aligned bases with even pitches load the
+ * updates' operands 16 bytes at a time, everything else 8.
+ * MPX_ERR_ARG before any pointer is touched: n < 0, nrhs < 0, pitch < n,
+ * pitch_b < nrhs, a null pointer. n = 0 and nrhs = 0 are no-ops. No workspace,
+ * no allocation, no synchronisation; everything runs on the given stream. */
+int mpx_chol_factor_f64(double *a, int n, int64_t pitch, int32_t *info, void *stream);
+int mpx_chol_solve_f64(const double *l, int n, int64_t pitch, double *b, int nrhs, int64_t pitch_b, void *stream);
+/* Tuning-harness entry (tools/bench_cholesky.py): one phase of the panel step at
+ * column j0 (a multiple of 64 below n). phase 0: the diagonal block (it zeroes
+ * *info first when j0 == 0), 1: the panel solve, 2: the symmetric update alone
+ * (it leaves the next diagonal block updated, not factored). The three in order
+ * over every panel give the factorisation's bits. */
+int mpx_chol_phase_f64(double *a, int n, int64_t pitch, int32_t *info, int j0, int phase, void *stream);
+
 /* ---------------- CPU references (OpenMP, -O3, same numerics) ---------------- */
 int mpx_cpu_threads(void);
 void mpx_cpu_vsub_f64(const double *a, const double *b, double *c, int64_t n);
@@ -758,6 +799,11 @@ void mpx_cpu_lu_factor_batched_f64(double *a, int batch, int n, int64_t pitch, i
                                    int32_t *info);
 void mpx_cpu_lu_solve_batched_f64(const double *lu, int batch, int n, int64_t pitch, int64_t stride,
                                   const int32_t *piv, double *b, int nrhs, int64_t pitch_b, int64_t stride_b);
+/* the unblocked algorithm of mpx_chol_factor_f64 / mpx_chol_solve_f64 (info: a
+ * host word), OpenMP over the rows of a column; bad arguments write nothing but
+ * *info = 0 */
+void mpx_cpu_chol_factor_f64(double *a, int n, int64_t pitch, int32_t *info);
+void mpx_cpu_chol_solve_f64(const double *l, int n, int64_t pitch, double *b, int nrhs, int64_t pitch_b);
 
 #ifdef __cplusplus
 }

@@ -1227,3 +1227,55 @@ void mpx_cpu_lu_solve_batched_f64(const double *lu, int batch, int n, int64_t pi
     for (int m = 0; m < batch; ++m)
         mpx_cpu_lu_solve_f64(lu + m * stride, n, pitch, piv + (int64_t)m * n, b + m * stride_b, nrhs, pitch_b);
 }
+
+/* ---- lab4: dense Cholesky A = L L^T, lower storage (the contract is in capi.h) ---- */
+void mpx_cpu_chol_factor_f64(double *a, int n, int64_t pitch, int32_t *info) {
+    if (info) *info = 0;
+    if (!a || n <= 0 || pitch < n) return;
+    for (int j = 0; j < n; ++j) {
+        double *rj = a + j * pitch;
+        double t = rj[j];
+        for (int k = 0; k < j; ++k) t -= rj[k] * rj[k];
+        if (!(t > 0.0) && info && *info == 0) *info = j + 1; /* zero, negative and NaN; go on regardless */
+        const double d = sqrt(t);
+        rj[j] = d;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static) if ((int64_t)(n - j) * j > 16384)
+#endif
+        for (int i = j + 1; i < n; ++i) {
+            double *ri = a + i * pitch;
+            double s = ri[j];
+            for (int k = 0; k < j; ++k) s -= ri[k] * rj[k];
+            ri[j] = s / d;
+        }
+    }
+}
+
+void mpx_cpu_chol_solve_f64(const double *l, int n, int64_t pitch, double *b, int nrhs, int64_t pitch_b) {
+    if (!l || !b || n <= 0 || nrhs <= 0 || pitch < n || pitch_b < nrhs) return;
+    /* L y = b, then L^T x = y: row i takes the finished rows k, k ascending */
+    for (int i = 0; i < n; ++i) {
+        double *bi = b + i * pitch_b;
+        const double d = l[i * pitch + i];
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static) if ((int64_t)i * nrhs > 16384)
+#endif
+        for (int j = 0; j < nrhs; ++j) {
+            double s = bi[j];
+            for (int k = 0; k < i; ++k) s -= l[i * pitch + k] * b[k * pitch_b + j];
+            bi[j] = s / d;
+        }
+    }
+    for (int i = n - 1; i >= 0; --i) {
+        double *bi = b + i * pitch_b;
+        const double d = l[i * pitch + i];
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static) if ((int64_t)(n - i) * nrhs > 16384)
+#endif
+        for (int j = 0; j < nrhs; ++j) {
+            double s = bi[j];
+            for (int k = i + 1; k < n; ++k) s -= l[k * pitch + i] * b[k * pitch_b + j];
+            bi[j] = s / d;
+        }
+    }
+}

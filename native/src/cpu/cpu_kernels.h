@@ -51,6 +51,11 @@ void mpx_cpu_lu_factor_batched_f64(double *a, int batch, int n, int64_t pitch, i
                                    int32_t *info);
 void mpx_cpu_lu_solve_batched_f64(const double *lu, int batch, int n, int64_t pitch, int64_t stride,
                                   const int32_t *piv, double *b, int nrhs, int64_t pitch_b, int64_t stride_b);
+/* lab4: unblocked Cholesky A = L L^T in lower storage and the solve with L, the
+ * contract of mpx_chol_factor_f64 / mpx_chol_solve_f64 (capi.h); bad arguments
+ * write nothing but *info = 0. */
+void mpx_cpu_chol_factor_f64(double *a, int n, int64_t pitch, int32_t *info);
+void mpx_cpu_chol_solve_f64(const double *l, int n, int64_t pitch, double *b, int nrhs, int64_t pitch_b);
 
 /* lab1 host text I/O (reference lab1/src/main.cu:46-52 scanf per value,
  * :82-84 printf per value), parallel over OpenMP threads in the -fopenmp builds
