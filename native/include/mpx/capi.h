@@ -718,7 +718,11 @@ int mpx_lu_solve_batched_f64(const double *lu, int batch, int n, int64_t pitch, 
  * whole factor for n <= 64) equal mpx_cpu_chol_factor_f64's bit for bit; from
  * column 64 on the MFMA's unspecified accumulation order is in every element,
  * and the yardsticks are exact recovery and the backward-error bounds
- * (tests/test_cholesky.py).
+ * (tests/test_cholesky.py). What holds bit for bit at any n: an element of L
+ * depends on the leading rows and columns only (chol(A[:m, :m]) is the leading
+ * block of chol(A), a block-diagonal matrix factors block by block), and the
+ * columns of B are independent systems, NaN and infinite ones included
+ * (tests/test_cholesky_invariants.py).
  * solve: B (n x nrhs, row-major, pitch_b) <- A^-1 B with L:
  *   acc = b_i;  for k = 0 .. i-1 ascending:    acc -= l_ik y_k;   y_i = acc / l_ii
  *   acc = y_i;  for k = i+1 .. n-1 ascending:  acc -= l_ki x_k;   x_i = acc / l_ii
