@@ -200,6 +200,12 @@ _SIGNATURES = {
     "mpx_chol_phase_f64": (c_int, [c_vp, c_int, c_i64, c_vp, c_int, c_int, c_vp]),
     "mpx_cpu_chol_factor_f64": (None, [c_vp, c_int, c_i64, c_vp]),
     "mpx_cpu_chol_solve_f64": (None, [c_vp, c_int, c_i64, c_vp, c_int, c_i64]),
+    # batched Cholesky (chol_batched.hip): factor (a, batch, n, pitch, stride, info, stream),
+    # solve (l, batch, n, pitch, stride, b, nrhs, pitch_b, stride_b, stream)
+    "mpx_chol_factor_batched_f64": (c_int, [c_vp, c_int, c_int, c_i64, c_i64, c_vp, c_vp]),
+    "mpx_chol_solve_batched_f64": (c_int, [c_vp, c_int, c_int, c_i64, c_i64, c_vp, c_int, c_i64, c_i64, c_vp]),
+    "mpx_cpu_chol_factor_batched_f64": (None, [c_vp, c_int, c_int, c_i64, c_i64, c_vp]),
+    "mpx_cpu_chol_solve_batched_f64": (None, [c_vp, c_int, c_int, c_i64, c_i64, c_vp, c_int, c_i64, c_i64]),
     "mpx_rows_checksum":(c_int, [c_vp, c_i64, c_int, c_i64, c_int, c_vp, c_vp]),
     "mpx_peer_probe_run": (c_int, [c_vp, c_vp]),
     "mpx_halo_fetch_run": (c_int, [c_vp, c_vp]),

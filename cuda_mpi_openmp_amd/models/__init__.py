@@ -7,6 +7,7 @@ form and a row/shard-decomposed multi-GPU form:
   lab4  DenseLU                                dense fp64 LU: solve, log-determinant, inverse (one device)
   lab4  BatchedDenseLU                         the same for a batch of small matrices, one launch each way
   lab4  DenseCholesky                          dense fp64 Cholesky of an SPD matrix: solve, log-determinant, inverse
+  lab4  BatchedDenseCholesky                   the same for a batch of small SPD matrices, one launch each way
   stencil  SlabJacobi                          2-D Jacobi with halo exchange
   stencil  SlabJacobi3D                        3-D Jacobi on plane slabs
   stencil  PoissonMultigrid                    2-D Poisson by geometric multigrid V-cycles (one device)
@@ -14,7 +15,7 @@ form and a row/shard-decomposed multi-GPU form:
 """
 
 from .classifier import PixelClassifier, SlabPixelClassifier
-from .dense import BatchedDenseLU, DenseCholesky, DenseLU
+from .dense import BatchedDenseCholesky, BatchedDenseLU, DenseCholesky, DenseLU
 from .edge import EdgeDetector, SlabEdgeDetector
 from .jacobi import SlabJacobi
 from .jacobi3d import SlabJacobi3D
@@ -24,4 +25,4 @@ from .vector import ShardedVectorSub, VectorSub
 
 __all__ = ["PixelClassifier", "SlabPixelClassifier", "EdgeDetector", "SlabEdgeDetector", "SlabJacobi", "SlabJacobi3D",
            "PoissonMultigrid", "PoissonMultigrid3D", "ShardedVectorSub", "VectorSub", "DenseLU",
-           "BatchedDenseLU", "DenseCholesky"]
+           "BatchedDenseLU", "DenseCholesky", "BatchedDenseCholesky"]

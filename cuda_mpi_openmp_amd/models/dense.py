@@ -13,6 +13,11 @@ singular member raises at construction, naming its batch index and column.
 lower triangle is what counts): half the work and no pivot search
 (``ops.cholesky_factor``). A matrix that is not positive definite raises at
 construction, naming the column where the factorisation broke down.
+
+``BatchedDenseCholesky`` is ``BatchedDenseLU`` for a batch of small symmetric
+positive definite matrices (``ops.cholesky_factor_batched``): one launch each
+way; a member that is not positive definite raises at construction, naming its
+batch index and column.
 """
 
 from __future__ import annotations
@@ -76,3 +81,23 @@ class DenseCholesky:
 
     def inverse(self) -> torch.Tensor:
         return ops.cholesky_solve_(self.l, torch.eye(self.n, dtype=torch.float64, device=self.l.device))
+
+
+class BatchedDenseCholesky:
+    def __init__(self, a: torch.Tensor):
+        self.l, info = ops.cholesky_factor_batched(a)
+        for m, k in enumerate(info.tolist()):
+            if k:
+                raise RuntimeError(f"BatchedDenseCholesky: matrix {m} of the batch is not positive definite "
+                                   f"(column {k - 1})")
+        self.batch, self.n = self.l.shape[0], self.l.shape[1]
+
+    def solve(self, b: torch.Tensor) -> torch.Tensor:
+        return ops.cholesky_solve_batched(self.l, b)
+
+    def logdet(self) -> torch.Tensor:
+        return ops.logdet_spd_batched(self.l)
+
+    def inverse(self) -> torch.Tensor:
+        eye = torch.eye(self.n, dtype=torch.float64, device=self.l.device)
+        return ops.cholesky_solve_batched_(self.l, eye.repeat(self.batch, 1, 1))

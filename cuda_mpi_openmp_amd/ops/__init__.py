@@ -5,7 +5,9 @@ from .classify import class_stats, classify_
 from .classify import plan as classify_plan
 from .edge import ConvLauncher, conv, conv_rows, roberts, roberts_rgb
 from .filters import Filter, get_filter, list_filters
-from .linalg import (cholesky_factor, cholesky_factor_, cholesky_solve, cholesky_solve_, logdet_spd, lu_factor,
+from .linalg import (cholesky_factor, cholesky_factor_, cholesky_factor_batched, cholesky_factor_batched_,
+                     cholesky_solve, cholesky_solve_, cholesky_solve_batched, cholesky_solve_batched_, logdet_spd,
+                     logdet_spd_batched, solve_spd_batched, lu_factor,
                      lu_factor_, lu_factor_batched, lu_factor_batched_, lu_solve, lu_solve_, lu_solve_batched, lu_solve_batched_, lu_unpack, lu_unpack_batched, slogdet, slogdet_batched, solve,
                      solve_batched, solve_spd)
 from .multigrid import (jacobi_relax, mg_prolong_add_, mg_prolong_cubic, mg_residual, mg_restrict, mg_tail,
@@ -70,5 +72,11 @@ __all__ = [
     "cholesky_solve_",
     "solve_spd",
     "logdet_spd",
+    "cholesky_factor_batched",
+    "cholesky_factor_batched_",
+    "cholesky_solve_batched",
+    "cholesky_solve_batched_",
+    "solve_spd_batched",
+    "logdet_spd_batched",
     "vsub",
 ]

@@ -15,7 +15,9 @@ backward-error bounds of LU, not bit for bit (tests/test_lu.py).
 The ``*_batched`` functions take ``(B, n, n)``. For n <= 64 the whole batch is
 one launch of plain VALU kernels in the CPU reference's operation order
 (lu_batched.hip), and there GPU and CPU do agree bit for bit, matrix by matrix
-(tests/test_lu_batched.py); larger n loops over the single-matrix kernels."""
+(tests/test_lu_batched.py); larger n loops over the single-matrix kernels. The
+same holds for ``cholesky_*_batched``, ``solve_spd_batched`` and
+``logdet_spd_batched`` (chol_batched.hip, tests/test_cholesky_batched.py)."""
 
 from __future__ import annotations
 
@@ -241,27 +243,28 @@ def lu_factor_batched(a: torch.Tensor):
     return lu_factor_batched_(a.clone(memory_format=torch.contiguous_format))
 
 
-def _check_solve_batched(lu: torch.Tensor, piv: torch.Tensor, b: torch.Tensor):
-    batch, n, pitch, stride = _check_batch(lu, "LU")
-    _check_batch_piv(piv, lu, batch, n)
+def _check_batch_b(b: torch.Tensor, factors: torch.Tensor, what: str, batch: int, n: int) -> None:
     if not isinstance(b, torch.Tensor) or b.dtype != torch.float64:
         raise ValueError("B must be float64 (fp64 only)")
     if b.dim() not in (2, 3):
         raise ValueError(f"B must be (batch, n) or (batch, n, k), not {b.dim()}-D")
     if b.shape[0] != batch or b.shape[1] != n:
         raise ValueError(f"B must be ({batch}, {n}) or ({batch}, {n}, k), not {tuple(b.shape)}")
-    if b.device != lu.device:
-        raise ValueError(f"LU is on {lu.device}, B on {b.device}")
+    if b.device != factors.device:
+        raise ValueError(f"{what} is on {factors.device}, B on {b.device}")
+
+
+def _check_solve_batched(lu: torch.Tensor, piv: torch.Tensor, b: torch.Tensor):
+    batch, n, pitch, stride = _check_batch(lu, "LU")
+    _check_batch_piv(piv, lu, batch, n)
+    _check_batch_b(b, lu, "LU", batch, n)
     return batch, n, pitch, stride
 
 
-def lu_solve_batched_(lu: torch.Tensor, piv: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """Solve A_m X_m = B_m in place in ``b`` ((B, n, k) or (B, n), float64) with
-    the factors of ``lu_factor_batched``: per matrix exactly ``lu_solve_`` of the
-    CPU reference (bit for bit for n <= 64, one launch). A 3-D ``b`` needs
-    contiguous rows; any row stride >= k and batch stride >= (n - 1) * stride(1)
-    + k are honoured. A 2-D ``b`` may have any positive element stride."""
-    batch, n, pitch, stride = _check_solve_batched(lu, piv, b)
+def _batch_b_layout(b: torch.Tensor, batch: int, n: int):
+    """``(nrhs, pitch_b, stride_b)`` of a checked batched right-hand side that is
+    solved in place: a 3-D ``b`` needs contiguous rows, a 2-D one any positive
+    element stride, and the members must not overlap."""
     if b.dim() == 2:
         nrhs = 1
         if n > 1 and b.stride(1) < 1:
@@ -277,9 +280,19 @@ def lu_solve_batched_(lu: torch.Tensor, piv: torch.Tensor, b: torch.Tensor) -> t
     span_b = (n - 1) * pitch_b + nrhs
     if batch > 1 and n and nrhs and b.stride(0) < span_b:
         raise ValueError("B must have a batch stride of at least (n - 1) * stride(1) + k")
+    return nrhs, pitch_b, (b.stride(0) if batch > 1 else span_b)
+
+
+def lu_solve_batched_(lu: torch.Tensor, piv: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Solve A_m X_m = B_m in place in ``b`` ((B, n, k) or (B, n), float64) with
+    the factors of ``lu_factor_batched``: per matrix exactly ``lu_solve_`` of the
+    CPU reference (bit for bit for n <= 64, one launch). A 3-D ``b`` needs
+    contiguous rows; any row stride >= k and batch stride >= (n - 1) * stride(1)
+    + k are honoured. A 2-D ``b`` may have any positive element stride."""
+    batch, n, pitch, stride = _check_solve_batched(lu, piv, b)
+    nrhs, pitch_b, stride_b = _batch_b_layout(b, batch, n)
     if batch == 0 or n == 0 or nrhs == 0:
         return b
-    stride_b = b.stride(0) if batch > 1 else span_b
     L = _native.lib()
     if lu.is_cuda:
         with torch.cuda.device(lu.device):
@@ -456,3 +469,96 @@ def logdet_spd(l: torch.Tensor) -> torch.Tensor:
     float64 tensor, no host read)."""
     _check_matrix(l, "L")
     return 2.0 * torch.log(torch.diagonal(l)).sum()
+
+
+# ---------------------------------------------------------------- batched Cholesky: (B, n, n), lower storage
+def cholesky_factor_batched_(a: torch.Tensor):
+    """Cholesky factorisation of every member of a float64 batch ``(B, n, n)``
+    of symmetric positive definite matrices, in place, lower storage: per
+    member exactly ``cholesky_factor_`` of the CPU reference (bit for bit for
+    n <= 64, where the whole batch is one launch of chol_batched.hip; larger n
+    loops over ``cholesky_factor_``'s kernels). Only the lower triangles
+    (diagonals included) are read or written. Rows must be contiguous; any row
+    stride >= n and any batch stride >= (n - 1) * stride(1) + n are honoured (a
+    slice of a larger buffer works, its padding is never touched). Returns
+    ``(a, info (B,) int32)``; ``info[m]`` is 0, or j + 1 for member m's first
+    column whose reduced diagonal is not > 0 (zero, negative or NaN); such a
+    member changes nothing in any other. No host synchronisation."""
+    batch, n, pitch, stride = _check_batch(a, "A")
+    if batch == 0 or n == 0:
+        return a, torch.zeros(batch, dtype=torch.int32, device=a.device)
+    info = torch.empty(batch, dtype=torch.int32, device=a.device)
+    L = _native.lib()
+    if a.is_cuda:
+        with torch.cuda.device(a.device):
+            _native.check(L.mpx_chol_factor_batched_f64(a.data_ptr(), batch, n, pitch, stride, info.data_ptr(),
+                                                        _native.stream_of(a)))
+    else:
+        L.mpx_cpu_chol_factor_batched_f64(a.data_ptr(), batch, n, pitch, stride, info.data_ptr())
+    return a, info
+
+
+def cholesky_factor_batched(a: torch.Tensor):
+    """``cholesky_factor_batched_`` on a contiguous copy; ``a`` is left
+    untouched (the copy's upper triangles are ``a``'s)."""
+    _check_batch(a, "A")
+    return cholesky_factor_batched_(a.clone(memory_format=torch.contiguous_format))
+
+
+def _check_cholesky_solve_batched(l: torch.Tensor, b: torch.Tensor):
+    batch, n, pitch, stride = _check_batch(l, "L")
+    _check_batch_b(b, l, "L", batch, n)
+    return batch, n, pitch, stride
+
+
+def cholesky_solve_batched_(l: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Solve A_m X_m = B_m in place in ``b`` ((B, n, k) or (B, n), float64) with
+    the factors of ``cholesky_factor_batched``: per member exactly
+    ``cholesky_solve_`` of the CPU reference (bit for bit for n <= 64, one
+    launch); only L's lower triangles are read. ``b`` has
+    ``lu_solve_batched_``'s stride rules."""
+    batch, n, pitch, stride = _check_cholesky_solve_batched(l, b)
+    nrhs, pitch_b, stride_b = _batch_b_layout(b, batch, n)
+    if batch == 0 or n == 0 or nrhs == 0:
+        return b
+    L = _native.lib()
+    if l.is_cuda:
+        with torch.cuda.device(l.device):
+            _native.check(L.mpx_chol_solve_batched_f64(l.data_ptr(), batch, n, pitch, stride, b.data_ptr(), nrhs,
+                                                       pitch_b, stride_b, _native.stream_of(l)))
+    else:
+        L.mpx_cpu_chol_solve_batched_f64(l.data_ptr(), batch, n, pitch, stride, b.data_ptr(), nrhs, pitch_b, stride_b)
+    return b
+
+
+def cholesky_solve_batched(l: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """``cholesky_solve_batched_`` on a contiguous copy of ``b``."""
+    _check_cholesky_solve_batched(l, b)
+    return cholesky_solve_batched_(l, b.clone(memory_format=torch.contiguous_format))
+
+
+def _raise_if_not_spd(info: torch.Tensor, who: str) -> None:
+    """The one host read: the first member that is not positive definite and its column."""
+    for m, k in enumerate(info.tolist()):
+        if k:
+            raise RuntimeError(f"{who}: matrix {m} of the batch is not positive definite (column {k - 1})")
+
+
+def solve_spd_batched(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """X with A_m X_m = B_m for symmetric positive definite members (their
+    lower triangles are what counts): factor a copy of ``a``, read ``info`` (the
+    one host read), solve on a copy of ``b``. A member that is not positive
+    definite raises ``RuntimeError`` naming the first such batch index and the
+    column where its factorisation broke down."""
+    batch, n, _, _ = _check_batch(a, "A")
+    _check_batch_b(b, a, "A", batch, n)
+    l, info = cholesky_factor_batched(a)
+    _raise_if_not_spd(info, "solve_spd_batched")
+    return cholesky_solve_batched(l, b)
+
+
+def logdet_spd_batched(l: torch.Tensor) -> torch.Tensor:
+    """log det A_m = 2 Σ log l_ii from the factors of ``cholesky_factor_batched``
+    (a ``(B,)`` float64 tensor, no host read)."""
+    _check_batch(l, "L")
+    return 2.0 * torch.log(torch.diagonal(l, dim1=1, dim2=2)).sum(dim=1)

@@ -742,6 +742,48 @@ int mpx_chol_solve_f64(const double *l, int n, int64_t pitch, double *b, int nrh
  * over every panel give the factorisation's bits. */
 int mpx_chol_phase_f64(double *a, int n, int64_t pitch, int32_t *info, int j0, int phase, void *stream);
 
+/* Batched: `batch` symmetric positive definite n x n matrices of one size
+ * (native/src/kernels/chol_batched.hip). Member m starts at a + m * stride, its
+ * rows are pitch >= n elements apart, and stride >= (n - 1) * pitch + n for
+ * batch > 1 (64-bit arithmetic, the product must not wrap). Per member the
+ * contract is exactly mpx_chol_factor_f64 / mpx_chol_solve_f64 above: lower
+ * storage, in place; only the lower triangle, diagonal included, is read or
+ * written, and the strict upper triangle, the pitch padding and the gap between
+ * members are never read and never written. info is batch int32 device words,
+ * every one written by the call and nothing outside info[0 .. batch): 0, or
+ * j + 1 for that member's first column whose reduced diagonal is not > 0 (zero,
+ * negative and NaN alike); columns before it are valid in every row, the rest
+ * of that member's triangle is unspecified, and no other member is affected.
+ * B's member m starts at b + m * stride_b, rows pitch_b >= nrhs apart,
+ * stride_b >= (n - 1) * pitch_b + nrhs.
+ * n <= 64: per member the result is exactly what mpx_cpu_chol_factor_f64 /
+ * mpx_cpu_chol_solve_f64 produce for that member alone, bit for bit:
+ * t = a_ij, t = t - (l_ik * l_jk) for k ascending with every operation rounded
+ * once (no FMA), l_jj = sqrt(t) correctly rounded, l_ij = t / l_jj by IEEE
+ * division; forward substitution acc -= l_ik y_k for k ascending, then / l_ii,
+ * back substitution acc -= l_ki x_k for k = i + 1 .. n - 1 ascending, then
+ * / l_ii. The factorisation is one launch: a lane holds one row in registers
+ * (padded to 8 / 16 / 32 / 64 columns, 64 / padded width members per wave),
+ * right-looking: at column j the reduced diagonal is broadcast within the
+ * member's lanes, the rows below divide and publish column j through LDS, and
+ * every lane subtracts the k = j term from its elements j + 1 .. row. The lower
+ * triangles are read and written once; info is written by the kernel. The solve
+ * is one launch: a lane is one (member, right-hand side) pair,
+ * 64 / min(nrhs, 64) members per wave, ceil(nrhs / 64) chunks.
+ * n > 64: correct, not fast. A loop over the members through
+ * mpx_chol_factor_f64 / mpx_chol_solve_f64 on the same stream; the yardstick
+ * there is the single-matrix one (exact recovery and the backward-error
+ * bounds), not bits.
+ * MPX_ERR_ARG before any pointer is touched: batch < 0, n < 0, nrhs < 0,
+ * pitch < n, pitch_b < nrhs, a short stride, a null pointer, batch x nrhs
+ * beyond the blocks of one launch. batch = 0, n = 0 and nrhs = 0 are no-ops. No
+ * workspace, no allocation, no host synchronisation, everything on the given
+ * stream. */
+int mpx_chol_factor_batched_f64(double *a, int batch, int n, int64_t pitch, int64_t stride, int32_t *info,
+                                void *stream);
+int mpx_chol_solve_batched_f64(const double *l, int batch, int n, int64_t pitch, int64_t stride, double *b, int nrhs,
+                               int64_t pitch_b, int64_t stride_b, void *stream);
+
 /* ---------------- CPU references (OpenMP, -O3, same numerics) ---------------- */
 int mpx_cpu_threads(void);
 void mpx_cpu_vsub_f64(const double *a, const double *b, double *c, int64_t n);
@@ -808,6 +850,12 @@ void mpx_cpu_lu_solve_batched_f64(const double *lu, int batch, int n, int64_t pi
  * *info = 0 */
 void mpx_cpu_chol_factor_f64(double *a, int n, int64_t pitch, int32_t *info);
 void mpx_cpu_chol_solve_f64(const double *l, int n, int64_t pitch, double *b, int nrhs, int64_t pitch_b);
+/* the batched Cholesky entries' reference and what CPU tensors run: an OpenMP
+ * loop over the members that calls the two functions above (info: batch host
+ * words); bad arguments write nothing */
+void mpx_cpu_chol_factor_batched_f64(double *a, int batch, int n, int64_t pitch, int64_t stride, int32_t *info);
+void mpx_cpu_chol_solve_batched_f64(const double *l, int batch, int n, int64_t pitch, int64_t stride, double *b,
+                                    int nrhs, int64_t pitch_b, int64_t stride_b);
 
 #ifdef __cplusplus
 }

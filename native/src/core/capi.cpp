@@ -41,6 +41,7 @@ const void *module_anchor_mg_tail();
 const void *module_anchor_lu();
 const void *module_anchor_lu_batched();
 const void *module_anchor_chol();
+const void *module_anchor_chol_batched();
 }  // namespace mpx
 
 extern "C" int mpx_preload_modules(void) {
@@ -50,7 +51,8 @@ extern "C" int mpx_preload_modules(void) {
                              mpx::module_anchor_edge_stream(), mpx::module_anchor_jacobi3d(),
                              mpx::module_anchor_multigrid(),    mpx::module_anchor_multigrid3d(),
                              mpx::module_anchor_mg_tail(),      mpx::module_anchor_lu(),
-                             mpx::module_anchor_lu_batched(),   mpx::module_anchor_chol()};
+                             mpx::module_anchor_lu_batched(),   mpx::module_anchor_chol(),
+                             mpx::module_anchor_chol_batched()};
     for (const void *k : anchors) {
         hipFuncAttributes attr;
         MPX_RETURN_IF_HIP_ERROR(hipFuncGetAttributes(&attr, k));

@@ -1279,3 +1279,23 @@ void mpx_cpu_chol_solve_f64(const double *l, int n, int64_t pitch, double *b, in
         }
     }
 }
+
+/* batched: every member on its own through the two functions above (their
+ * inner OpenMP regions run serially inside this one) */
+void mpx_cpu_chol_factor_batched_f64(double *a, int batch, int n, int64_t pitch, int64_t stride, int32_t *info) {
+    if (!a || !info || batch <= 0 || n < 0 || pitch < n) return;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static)
+#endif
+    for (int m = 0; m < batch; ++m) mpx_cpu_chol_factor_f64(a + m * stride, n, pitch, info + m);
+}
+
+void mpx_cpu_chol_solve_batched_f64(const double *l, int batch, int n, int64_t pitch, int64_t stride, double *b,
+                                    int nrhs, int64_t pitch_b, int64_t stride_b) {
+    if (!l || !b || batch <= 0) return;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static)
+#endif
+    for (int m = 0; m < batch; ++m)
+        mpx_cpu_chol_solve_f64(l + m * stride, n, pitch, b + m * stride_b, nrhs, pitch_b);
+}

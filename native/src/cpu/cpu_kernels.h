@@ -56,6 +56,13 @@ void mpx_cpu_lu_solve_batched_f64(const double *lu, int batch, int n, int64_t pi
  * write nothing but *info = 0. */
 void mpx_cpu_chol_factor_f64(double *a, int n, int64_t pitch, int32_t *info);
 void mpx_cpu_chol_solve_f64(const double *l, int n, int64_t pitch, double *b, int nrhs, int64_t pitch_b);
+/* The same for `batch` matrices (member m at a + m * stride, one info word each;
+ * B's members stride_b apart): an OpenMP loop over the members that calls the
+ * two functions above, so every member gets exactly their result. Bad arguments
+ * write nothing. */
+void mpx_cpu_chol_factor_batched_f64(double *a, int batch, int n, int64_t pitch, int64_t stride, int32_t *info);
+void mpx_cpu_chol_solve_batched_f64(const double *l, int batch, int n, int64_t pitch, int64_t stride, double *b,
+                                    int nrhs, int64_t pitch_b, int64_t stride_b);
 
 /* lab1 host text I/O (reference lab1/src/main.cu:46-52 scanf per value,
  * :82-84 printf per value), parallel over OpenMP threads in the -fopenmp builds
