@@ -206,6 +206,18 @@ _SIGNATURES = {
     "mpx_chol_solve_batched_f64": (c_int, [c_vp, c_int, c_int, c_i64, c_i64, c_vp, c_int, c_i64, c_i64, c_vp]),
     "mpx_cpu_chol_factor_batched_f64": (None, [c_vp, c_int, c_int, c_i64, c_i64, c_vp]),
     "mpx_cpu_chol_solve_batched_f64": (None, [c_vp, c_int, c_int, c_i64, c_i64, c_vp, c_int, c_i64, c_i64]),
+    # lab4 QR (qr.hip): factor (a, m, n, pitch, tau, info, ws, ws_bytes, stream),
+    # apply (qr, m, n, pitch, tau, b, nrhs, pitch_b, transpose, ws, ws_bytes, stream),
+    # rsolve (qr, n, pitch, b, nrhs, pitch_b, stream), phase (a, m, n, pitch, tau, info, j0, phase, ws, ...)
+    "mpx_qr_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
+    "mpx_qr_factor_f64": (c_int, [c_vp, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "mpx_qr_apply_f64": (c_int, [c_vp, c_int, c_int, c_i64, c_vp, c_vp, c_int, c_i64, c_int, c_vp, c_i64, c_vp]),
+    "mpx_qr_rsolve_f64": (c_int, [c_vp, c_int, c_i64, c_vp, c_int, c_i64, c_vp]),
+    "mpx_qr_plan": (c_int, [c_int, c_int, c_vp]),
+    "mpx_qr_phase_f64": (c_int, [c_vp, c_int, c_int, c_i64, c_vp, c_vp, c_int, c_int, c_vp, c_i64, c_vp]),
+    "mpx_cpu_qr_factor_f64": (None, [c_vp, c_int, c_int, c_i64, c_vp, c_vp]),
+    "mpx_cpu_qr_apply_f64": (None, [c_vp, c_int, c_int, c_i64, c_vp, c_vp, c_int, c_i64, c_int]),
+    "mpx_cpu_qr_rsolve_f64": (None, [c_vp, c_int, c_i64, c_vp, c_int, c_i64]),
     "mpx_rows_checksum":(c_int, [c_vp, c_i64, c_int, c_i64, c_int, c_vp, c_vp]),
     "mpx_peer_probe_run": (c_int, [c_vp, c_vp]),
     "mpx_halo_fetch_run": (c_int, [c_vp, c_vp]),

@@ -8,6 +8,7 @@ form and a row/shard-decomposed multi-GPU form:
   lab4  BatchedDenseLU                         the same for a batch of small matrices, one launch each way
   lab4  DenseCholesky                          dense fp64 Cholesky of an SPD matrix: solve, log-determinant, inverse
   lab4  BatchedDenseCholesky                   the same for a batch of small SPD matrices, one launch each way
+  lab4  DenseQR                                dense fp64 Householder QR (m >= n): least squares, Q, R, log|det|
   stencil  SlabJacobi                          2-D Jacobi with halo exchange
   stencil  SlabJacobi3D                        3-D Jacobi on plane slabs
   stencil  PoissonMultigrid                    2-D Poisson by geometric multigrid V-cycles (one device)
@@ -15,7 +16,7 @@ form and a row/shard-decomposed multi-GPU form:
 """
 
 from .classifier import PixelClassifier, SlabPixelClassifier
-from .dense import BatchedDenseCholesky, BatchedDenseLU, DenseCholesky, DenseLU
+from .dense import BatchedDenseCholesky, BatchedDenseLU, DenseCholesky, DenseLU, DenseQR
 from .edge import EdgeDetector, SlabEdgeDetector
 from .jacobi import SlabJacobi
 from .jacobi3d import SlabJacobi3D
@@ -25,4 +26,4 @@ from .vector import ShardedVectorSub, VectorSub
 
 __all__ = ["PixelClassifier", "SlabPixelClassifier", "EdgeDetector", "SlabEdgeDetector", "SlabJacobi", "SlabJacobi3D",
            "PoissonMultigrid", "PoissonMultigrid3D", "ShardedVectorSub", "VectorSub", "DenseLU",
-           "BatchedDenseLU", "DenseCholesky", "BatchedDenseCholesky"]
+           "BatchedDenseLU", "DenseCholesky", "BatchedDenseCholesky", "DenseQR"]

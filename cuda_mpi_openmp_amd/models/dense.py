@@ -18,6 +18,13 @@ construction, naming the column where the factorisation broke down.
 positive definite matrices (``ops.cholesky_factor_batched``): one launch each
 way; a member that is not positive definite raises at construction, naming its
 batch index and column.
+
+``DenseQR`` factors a tall or square matrix (m >= n) by Householder QR
+(``ops.qr_factor``) and answers least-squares problems from the factors:
+``solve(b)`` minimises ``‖A x − b‖₂``, ``q()`` and ``r()`` unpack the thin Q and
+R, ``mul_q(b, transpose=)`` applies the full Q or Qᵀ, ``logabsdet()`` is
+``log |det A|`` of a square matrix. A rank-deficient matrix (an exactly zero
+``R_jj``) raises at construction, naming the column.
 """
 
 from __future__ import annotations
@@ -101,3 +108,30 @@ class BatchedDenseCholesky:
     def inverse(self) -> torch.Tensor:
         eye = torch.eye(self.n, dtype=torch.float64, device=self.l.device)
         return ops.cholesky_solve_batched_(self.l, eye.repeat(self.batch, 1, 1))
+
+
+class DenseQR:
+    def __init__(self, a: torch.Tensor):
+        self.qr, self.tau, info = ops.qr_factor(a)
+        k = int(info.item())
+        if k:
+            raise RuntimeError(f"DenseQR: the matrix is rank-deficient (zero on R's diagonal in column {k - 1})")
+        self.m, self.n = self.qr.shape
+
+    def solve(self, b: torch.Tensor) -> torch.Tensor:
+        y = ops.qr_mul_q(self.qr, self.tau, b, transpose=True)
+        return ops.qr_solve_r_(self.qr, y[:self.n]).clone(memory_format=torch.contiguous_format)
+
+    def q(self) -> torch.Tensor:
+        return ops.qr_unpack(self.qr, self.tau)[0]
+
+    def r(self) -> torch.Tensor:
+        return torch.triu(self.qr[:self.n])
+
+    def mul_q(self, b: torch.Tensor, transpose: bool = False) -> torch.Tensor:
+        return ops.qr_mul_q(self.qr, self.tau, b, transpose)
+
+    def logabsdet(self) -> torch.Tensor:
+        if self.m != self.n:
+            raise ValueError(f"logabsdet needs a square matrix, not {(self.m, self.n)}")
+        return torch.log(torch.abs(torch.diagonal(self.qr))).sum()

@@ -1,5 +1,5 @@
 """lab4 operators: dense LU with partial pivoting in fp64 and what follows from
-its factors (solve, log-determinant, unpacking), and at the end of the file the
+its factors (solve, log-determinant, unpacking), and further down the
 Cholesky factorisation of symmetric positive definite matrices (``cholesky_*``,
 ``solve_spd``, ``logdet_spd``; the contract is capi.h's ``mpx_chol_factor_f64``). The matrix lab has no reference
 program, so the contract is this package's (capi.h, ``mpx_lu_factor_f64``):
@@ -11,6 +11,15 @@ GPU tensors run the gfx950 kernels (the trailing update on
 torch's allocator; CPU tensors run the unblocked OpenMP reference. The MFMA's
 accumulation order is unspecified, so the two agree to the componentwise
 backward-error bounds of LU, not bit for bit (tests/test_lu.py).
+
+The last section is Householder QR of a tall or square matrix (``qr_factor*``,
+``qr_mul_q*``, ``qr_solve_r_``, ``qr_unpack``, ``lstsq``; the contract is
+capi.h's ``mpx_qr_factor_f64``): LAPACK ``geqrf`` storage, ``dlarfg``'s sign rule
+without its rescaling. There too the GPU (block reflectors on the MFMA, its own
+fixed reduction orders over the rows) and the CPU reference (rows summed in
+ascending order) agree to Householder QR's backward-error bounds, not bit for
+bit, and exactly where every intermediate is exactly representable
+(tests/test_qr.py).
 
 The ``*_batched`` functions take ``(B, n, n)``. For n <= 64 the whole batch is
 one launch of plain VALU kernels in the CPU reference's operation order
@@ -562,3 +571,191 @@ def logdet_spd_batched(l: torch.Tensor) -> torch.Tensor:
     (a ``(B,)`` float64 tensor, no host read)."""
     _check_batch(l, "L")
     return 2.0 * torch.log(torch.diagonal(l, dim1=1, dim2=2)).sum(dim=1)
+
+
+# ---------------------------------------------------------------- Householder QR: m >= n, geqrf storage
+def _check_tall(a: torch.Tensor, what: str):
+    """``_check_matrix`` for a rectangular matrix with at least as many rows as columns."""
+    if not isinstance(a, torch.Tensor):
+        raise ValueError(f"{what} must be a tensor")
+    if a.dtype != torch.float64:
+        raise ValueError(f"{what} must be float64 (fp64 only), not {a.dtype}")
+    if a.dim() != 2:
+        raise ValueError(f"{what} must be 2-D, not {a.dim()}-D")
+    m, n = a.shape
+    if m < n:
+        raise ValueError(f"{what} must have at least as many rows as columns (m >= n), not {tuple(a.shape)}")
+    if m >= 2 ** 31:
+        raise ValueError(f"{what} is too large")
+    if m and n and a.stride(1) != 1:
+        raise ValueError(f"{what} must have contiguous rows (stride(1) == 1)")
+    if m > 1 and a.stride(0) < n:
+        raise ValueError(f"{what} must have a row stride of at least n")
+    return m, n
+
+
+def _check_tau(tau: torch.Tensor, qr: torch.Tensor, n: int) -> None:
+    if not isinstance(tau, torch.Tensor) or tau.dtype != torch.float64 or tau.dim() != 1 or tau.shape[0] != n:
+        raise ValueError(f"tau must be a float64 vector of {n} elements")
+    if not tau.is_contiguous():
+        raise ValueError("tau must be contiguous")
+    if tau.device != qr.device:
+        raise ValueError(f"QR is on {qr.device}, tau on {tau.device}")
+
+
+def _b_layout(b: torch.Tensor, rows: int):
+    """``(nrhs, pitch_b)`` of a right-hand side solved in place: ``lu_solve_``'s stride rules."""
+    if b.dim() == 1:
+        if rows > 1 and b.stride(0) < 1:
+            raise ValueError("B must have a positive stride")
+        return 1, (max(b.stride(0), 1) if rows > 1 else 1)
+    nrhs = b.shape[1]
+    if nrhs and b.stride(1) != 1:
+        raise ValueError("B must have contiguous rows (stride(1) == 1)")
+    if rows > 1 and b.stride(0) < nrhs:
+        raise ValueError("B must have a row stride of at least its width")
+    return nrhs, _pitch(b, nrhs)
+
+
+def qr_factor_(a: torch.Tensor):
+    """Householder QR A = Q R of a float64 matrix with m >= n, in place, in
+    LAPACK ``geqrf`` storage. Rows must be contiguous; any row stride >= n is
+    the pitch, and the padding is never read or written. Returns
+    ``(a, tau, info)``: R in the upper triangle of ``a[:n]``, column j below the
+    diagonal holds ``v_j[j+1:]`` (``v_j[j] = 1`` implied), ``tau`` n float64,
+    ``H_j = I - tau_j v_j v_jᵀ``, ``Q = H_0 H_1 … H_{n-1}``. The reflectors
+    follow LAPACK's ``dlarfg`` without its rescaling (capi.h,
+    ``mpx_qr_factor_f64``): ``beta = -copysign(sqrt(alpha² + sigma), alpha)``,
+    so the diagonal of R may be negative, and a column that is already zero
+    below its diagonal keeps ``tau = 0``. The sums of squares are plain fp64:
+    the squares of the entries must neither overflow nor underflow to zero.
+    ``info`` is a one-element int32 tensor on ``a``'s device: 0, or j + 1 for
+    the first column with ``R_jj == 0`` exactly; the factorisation runs on
+    regardless. Two runs give the same bits, and the factorisation of
+    ``a[:, :k]`` is the first k columns of that of ``a`` bit for bit. GPU
+    tensors run qr.hip on the current stream (one launch per column for the
+    panels, the block reflectors on ``v_mfma_f64_16x16x4_f64``), CPU tensors the
+    unblocked reference; the two agree to Householder QR's backward-error
+    bounds, not bit for bit (tests/test_qr.py). No host synchronisation."""
+    m, n = _check_tall(a, "A")
+    tau = torch.empty(n, dtype=torch.float64, device=a.device)
+    if m == 0 or n == 0:
+        return a, tau, torch.zeros(1, dtype=torch.int32, device=a.device)
+    info = torch.empty(1, dtype=torch.int32, device=a.device)
+    L = _native.lib()
+    if a.is_cuda:
+        nbytes = int(L.mpx_qr_workspace_bytes(m, n, 0))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
+        with torch.cuda.device(a.device):
+            _native.check(L.mpx_qr_factor_f64(a.data_ptr(), m, n, _pitch(a, n), tau.data_ptr(), info.data_ptr(),
+                                              ws.data_ptr(), nbytes, _native.stream_of(a)))
+    else:
+        L.mpx_cpu_qr_factor_f64(a.data_ptr(), m, n, _pitch(a, n), tau.data_ptr(), info.data_ptr())
+    return a, tau, info
+
+
+def qr_factor(a: torch.Tensor):
+    """``qr_factor_`` on a contiguous copy; ``a`` is left untouched."""
+    _check_tall(a, "A")
+    return qr_factor_(a.clone(memory_format=torch.contiguous_format))
+
+
+def _check_mul_q(qr: torch.Tensor, tau: torch.Tensor, b: torch.Tensor):
+    m, n = _check_tall(qr, "QR")
+    _check_tau(tau, qr, n)
+    if not isinstance(b, torch.Tensor) or b.dtype != torch.float64:
+        raise ValueError("B must be float64 (fp64 only)")
+    if b.dim() not in (1, 2):
+        raise ValueError(f"B must be (m,) or (m, k), not {b.dim()}-D")
+    if b.shape[0] != m:
+        raise ValueError(f"B has {b.shape[0]} rows, QR {m}")
+    if b.device != qr.device:
+        raise ValueError(f"QR is on {qr.device}, B on {b.device}")
+    return m, n
+
+
+def qr_mul_q_(qr: torch.Tensor, tau: torch.Tensor, b: torch.Tensor, transpose: bool = False) -> torch.Tensor:
+    """``b <- Q b`` (or ``Qᵀ b`` with ``transpose=True``) in place, Q the full
+    m x m orthogonal factor of ``qr_factor``, applied from the stored reflectors
+    (four launches per 64 of them on the GPU; T is rebuilt, never stored). ``b``
+    is (m,) or (m, k) float64 with ``lu_solve_``'s stride rules; its columns are
+    independent."""
+    m, n = _check_mul_q(qr, tau, b)
+    nrhs, pitch_b = _b_layout(b, m)
+    if m == 0 or n == 0 or nrhs == 0:
+        return b
+    L = _native.lib()
+    if qr.is_cuda:
+        nbytes = int(L.mpx_qr_workspace_bytes(m, n, nrhs))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=qr.device)
+        with torch.cuda.device(qr.device):
+            _native.check(L.mpx_qr_apply_f64(qr.data_ptr(), m, n, _pitch(qr, n), tau.data_ptr(), b.data_ptr(), nrhs,
+                                             pitch_b, 1 if transpose else 0, ws.data_ptr(), nbytes,
+                                             _native.stream_of(qr)))
+    else:
+        L.mpx_cpu_qr_apply_f64(qr.data_ptr(), m, n, _pitch(qr, n), tau.data_ptr(), b.data_ptr(), nrhs, pitch_b,
+                               1 if transpose else 0)
+    return b
+
+
+def qr_mul_q(qr: torch.Tensor, tau: torch.Tensor, b: torch.Tensor, transpose: bool = False) -> torch.Tensor:
+    """``qr_mul_q_`` on a contiguous copy of ``b``."""
+    _check_mul_q(qr, tau, b)
+    return qr_mul_q_(qr, tau, b.clone(memory_format=torch.contiguous_format), transpose)
+
+
+def qr_solve_r_(qr: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """``b <- R⁻¹ b`` in place by blocked back substitution with the upper
+    triangle of ``qr[:n]``; ``b`` is (n,) or (n, k) with ``lu_solve_``'s stride
+    rules. A zero on R's diagonal (``info`` of ``qr_factor``) divides by zero."""
+    _, n = _check_tall(qr, "QR")
+    if not isinstance(b, torch.Tensor) or b.dtype != torch.float64:
+        raise ValueError("B must be float64 (fp64 only)")
+    if b.dim() not in (1, 2):
+        raise ValueError(f"B must be (n,) or (n, k), not {b.dim()}-D")
+    if b.shape[0] != n:
+        raise ValueError(f"B has {b.shape[0]} rows, R {n}")
+    if b.device != qr.device:
+        raise ValueError(f"QR is on {qr.device}, B on {b.device}")
+    nrhs, pitch_b = _b_layout(b, n)
+    if n == 0 or nrhs == 0:
+        return b
+    L = _native.lib()
+    if qr.is_cuda:
+        with torch.cuda.device(qr.device):
+            _native.check(L.mpx_qr_rsolve_f64(qr.data_ptr(), n, _pitch(qr, n), b.data_ptr(), nrhs, pitch_b,
+                                              _native.stream_of(qr)))
+    else:
+        L.mpx_cpu_qr_rsolve_f64(qr.data_ptr(), n, _pitch(qr, n), b.data_ptr(), nrhs, pitch_b)
+    return b
+
+
+def qr_unpack(qr: torch.Tensor, tau: torch.Tensor):
+    """``(Q, R)`` with ``A = Q @ R``: the thin Q (m x n: Q applied to the
+    leading columns of the identity) and the n x n upper-triangular R."""
+    m, n = _check_tall(qr, "QR")
+    _check_tau(tau, qr, n)
+    q = torch.eye(m, n, dtype=torch.float64, device=qr.device)
+    return qr_mul_q_(qr, tau, q), torch.triu(qr[:n])
+
+
+def lstsq(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """The minimiser of ``‖A x − b‖₂`` for a float64 ``a`` with m >= n of full
+    column rank, by Householder QR: factor a copy of ``a``, read ``info`` (the
+    one host read), apply ``Qᵀ`` to a copy of ``b`` ((m,) or (m, k)), solve
+    with R. Returns (n,) or (n, k). A rank-deficient matrix (an exactly zero
+    ``R_jj``) raises ``RuntimeError`` naming the column. For m = n this is a
+    linear solve."""
+    m, n = _check_tall(a, "A")
+    if not isinstance(b, torch.Tensor) or b.dtype != torch.float64:
+        raise ValueError("B must be float64 (fp64 only)")
+    if b.dim() not in (1, 2) or b.shape[0] != m:
+        raise ValueError(f"B must be ({m},) or ({m}, k), not {tuple(b.shape)}")
+    if b.device != a.device:
+        raise ValueError(f"A is on {a.device}, B on {b.device}")
+    qr, tau, info = qr_factor(a)
+    k = int(info.item())
+    if k:
+        raise RuntimeError(f"lstsq: the matrix is rank-deficient (zero on R's diagonal in column {k - 1})")
+    y = qr_mul_q(qr, tau, b, transpose=True)
+    return qr_solve_r_(qr, y[:n]).clone(memory_format=torch.contiguous_format)

@@ -784,6 +784,74 @@ int mpx_chol_factor_batched_f64(double *a, int batch, int n, int64_t pitch, int6
 int mpx_chol_solve_batched_f64(const double *l, int batch, int n, int64_t pitch, int64_t stride, double *b, int nrhs,
                                int64_t pitch_b, int64_t stride_b, void *stream);
 
+/* lab4: Householder QR A = Q R of a tall or square m x n fp64 matrix (m >= n >= 0),
+ * row-major with a row pitch, in place, in LAPACK geqrf storage
+ * (native/src/kernels/qr.hip). On return the upper triangle of A[0:n, 0:n]
+ * holds R, column j below the diagonal holds v_j[j+1:m] (v_j[j] = 1 implied),
+ * tau is n doubles, H_j = I - tau_j v_j v_j^T and Q = H_0 H_1 .. H_{n-1}. The
+ * pitch padding is never read or written.
+ * Reflector j (LAPACK dlarfg's rule without its rescaling): alpha = a_jj,
+ * sigma = sum_{i > j} a_ij^2. sigma == 0 exactly: tau_j = 0 and the column is
+ * left as it is, so R_jj = alpha with its sign. Otherwise
+ *   norm = sqrt(alpha^2 + sigma)  (sqrt correctly rounded),
+ *   beta = -copysign(norm, alpha),  tau_j = (beta - alpha) / beta,
+ *   v_i = a_ij / (alpha - beta)  (an IEEE division, not a reciprocal),  R_jj = beta,
+ * and every column right of j takes w = tau_j (a_j,col + g_col / (alpha - beta))
+ * with g_col = sum_{i > j} a_ij a_i,col: a_j,col -= w, a_i,col -= v_i w. The
+ * diagonal of R may be negative; the last column of a square matrix has
+ * tau = 0. The sums of squares are plain fp64: a_ij^2 must neither overflow
+ * nor underflow to zero (no scaled norms).
+ * *info (a device word) is 0, or j + 1 for the first column with R_jj == 0
+ * exactly. The factorisation runs on regardless (nothing is singular for QR
+ * itself; only the triangular solve needs info). A NaN is not a zero: it
+ * propagates to its own column and the columns right of it, nowhere else.
+ * Panels of 64 columns, right-looking. One launch per panel column (and one
+ * more per panel): a rank-1 VALU update of the panel, per-workgroup partials of
+ * the next column's Gram row, folded in index order by the last workgroup to
+ * finish (a counter after __threadfence(), nobody ever waits). Then four
+ * launches per panel with columns to its right: W = V^T C and V^T V on
+ * v_mfma_f64_16x16x4_f64 with a K loop over the rows, cut into chunks of 1024
+ * rows whose partials are summed in ascending order; T (larft, forward,
+ * columnwise) by one workgroup; Z = T^T W; C -= V Z on the MFMA. A
+ * factorisation is n + 5 ceil(n / 64) + 1 launches at most. No floating-point
+ * atomics; every reduction over rows has a fixed order that depends on m, the
+ * pitch alignment class and the column's index alone: two runs give the same
+ * bits, and column j of the result depends only on columns 0 .. j of the input
+ * (the factorisation of A[:, :k] is the first k columns of that of A, bit for
+ * bit). The MFMA's accumulation order is unspecified and the reduction orders
+ * differ, so the GPU and the CPU reference agree to Householder QR's
+ * backward-error bounds, not bit for bit (tests/test_qr.py), and exactly
+ * wherever every intermediate is exactly representable.
+ * apply: B (m x nrhs, row-major, pitch_b) <- Q^T B (transpose != 0) or Q B from
+ * the stored reflectors, one block reflector I - V T V^T per panel, four
+ * launches each; T is rebuilt per panel and never stored across calls.
+ * rsolve: B (n x nrhs) <- R^-1 B with the upper triangle of qr[0:n, 0:n], blocked
+ * back substitution: substitution on the 64 x 64 diagonal blocks (never an
+ * inverse), the MFMA update between them.
+ * The workspace is the caller's, >= mpx_qr_workspace_bytes(m, n, nrhs) bytes
+ * (nrhs = 0 for the factorisation), 16-byte aligned and stream-ordered
+ * (mpx_sort_ws's rule); rsolve needs none.
+ * MPX_ERR_ARG before any pointer is touched: a negative size, m < n, pitch < n,
+ * pitch_b < nrhs, a null pointer, a short or misaligned workspace. m = 0, n = 0
+ * and nrhs = 0 are no-ops. No allocation, no host synchronisation. */
+int64_t mpx_qr_workspace_bytes(int m, int n, int nrhs);
+int mpx_qr_factor_f64(double *a, int m, int n, int64_t pitch, double *tau, int32_t *info, void *workspace,
+                      int64_t workspace_bytes, void *stream);
+int mpx_qr_apply_f64(const double *qr, int m, int n, int64_t pitch, const double *tau, double *b, int nrhs,
+                     int64_t pitch_b, int transpose, void *workspace, int64_t workspace_bytes, void *stream);
+int mpx_qr_rsolve_f64(const double *qr, int n, int64_t pitch, double *b, int nrhs, int64_t pitch_b, void *stream);
+/* The launcher's geometry for an m x n matrix, so that tests aim at the real
+ * chunking: out = {rows per workgroup of the panel kernel, rows of one W chunk,
+ * W chunks of the first panel, panel width}. */
+int mpx_qr_plan(int m, int n, int32_t out[4]);
+/* Tuning-harness entry (tools/bench_qr.py): one phase of the panel step at
+ * column j0 (a multiple of 64 below n). phase 0: the panel's columns (it zeroes
+ * *info first when j0 == 0), 1: W = V^T C and V^T V, 2: T and Z, 3: C -= V Z.
+ * Phases 1..3 do nothing for the last panel. The four in order over every panel
+ * give the factorisation's bits. */
+int mpx_qr_phase_f64(double *a, int m, int n, int64_t pitch, double *tau, int32_t *info, int j0, int phase,
+                     void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---------------- CPU references (OpenMP, -O3, same numerics) ---------------- */
 int mpx_cpu_threads(void);
 void mpx_cpu_vsub_f64(const double *a, const double *b, double *c, int64_t n);
@@ -856,6 +924,13 @@ void mpx_cpu_chol_solve_f64(const double *l, int n, int64_t pitch, double *b, in
 void mpx_cpu_chol_factor_batched_f64(double *a, int batch, int n, int64_t pitch, int64_t stride, int32_t *info);
 void mpx_cpu_chol_solve_batched_f64(const double *l, int batch, int n, int64_t pitch, int64_t stride, double *b,
                                     int nrhs, int64_t pitch_b, int64_t stride_b);
+/* the unblocked algorithm of mpx_qr_factor_f64 / mpx_qr_apply_f64 /
+ * mpx_qr_rsolve_f64 (info: a host word), rows summed in ascending order, OpenMP
+ * over the columns of the update; bad arguments write nothing but *info = 0 */
+void mpx_cpu_qr_factor_f64(double *a, int m, int n, int64_t pitch, double *tau, int32_t *info);
+void mpx_cpu_qr_apply_f64(const double *qr, int m, int n, int64_t pitch, const double *tau, double *b, int nrhs,
+                          int64_t pitch_b, int transpose);
+void mpx_cpu_qr_rsolve_f64(const double *qr, int n, int64_t pitch, double *b, int nrhs, int64_t pitch_b);
 
 #ifdef __cplusplus
 }

@@ -42,6 +42,7 @@ const void *module_anchor_lu();
 const void *module_anchor_lu_batched();
 const void *module_anchor_chol();
 const void *module_anchor_chol_batched();
+const void *module_anchor_qr();
 }  // namespace mpx
 
 extern "C" int mpx_preload_modules(void) {
@@ -52,7 +53,7 @@ extern "C" int mpx_preload_modules(void) {
                              mpx::module_anchor_multigrid(),    mpx::module_anchor_multigrid3d(),
                              mpx::module_anchor_mg_tail(),      mpx::module_anchor_lu(),
                              mpx::module_anchor_lu_batched(),   mpx::module_anchor_chol(),
-                             mpx::module_anchor_chol_batched()};
+                             mpx::module_anchor_chol_batched(), mpx::module_anchor_qr()};
     for (const void *k : anchors) {
         hipFuncAttributes attr;
         MPX_RETURN_IF_HIP_ERROR(hipFuncGetAttributes(&attr, k));

@@ -1299,3 +1299,74 @@ void mpx_cpu_chol_solve_batched_f64(const double *l, int batch, int n, int64_t p
     for (int m = 0; m < batch; ++m)
         mpx_cpu_chol_solve_f64(l + m * stride, n, pitch, b + m * stride_b, nrhs, pitch_b);
 }
+
+/* ---- lab4: dense Householder QR, geqrf storage (the contract is in capi.h) ---- */
+void mpx_cpu_qr_factor_f64(double *a, int m, int n, int64_t pitch, double *tau, int32_t *info) {
+    if (info) *info = 0;
+    if (!a || !tau || m <= 0 || n <= 0 || m < n || pitch < n) return;
+    for (int j = 0; j < n; ++j) {
+        double *rj = a + j * pitch;
+        const double alpha = rj[j];
+        double sigma = 0.0;
+        for (int i = j + 1; i < m; ++i) sigma += a[i * pitch + j] * a[i * pitch + j];
+        if (sigma == 0.0) { /* the column is left as it is: R_jj = alpha with its sign */
+            tau[j] = 0.0;
+            if (alpha == 0.0 && info && *info == 0) *info = j + 1;
+            continue;
+        }
+        const double norm = sqrt(alpha * alpha + sigma);
+        const double beta = -copysign(norm, alpha);
+        const double t = (beta - alpha) / beta, d = alpha - beta;
+        tau[j] = t;
+        if (beta == 0.0 && info && *info == 0) *info = j + 1;
+        /* the columns right of j first: they read column j unscaled, rows ascending */
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static) if ((int64_t)(m - j) * (n - j) > 16384)
+#endif
+        for (int col = j + 1; col < n; ++col) {
+            double g = 0.0;
+            for (int i = j + 1; i < m; ++i) g += a[i * pitch + j] * a[i * pitch + col];
+            const double w = t * (rj[col] + g / d);
+            rj[col] -= w;
+            for (int i = j + 1; i < m; ++i) a[i * pitch + col] -= (a[i * pitch + j] / d) * w;
+        }
+        for (int i = j + 1; i < m; ++i) a[i * pitch + j] = a[i * pitch + j] / d;
+        rj[j] = beta;
+    }
+}
+
+void mpx_cpu_qr_apply_f64(const double *qr, int m, int n, int64_t pitch, const double *tau, double *b, int nrhs,
+                          int64_t pitch_b, int transpose) {
+    if (!qr || !tau || !b || m <= 0 || n <= 0 || nrhs <= 0 || m < n || pitch < n || pitch_b < nrhs) return;
+    for (int q = 0; q < n; ++q) { /* Q^T = H_{n-1} .. H_0 takes H_0 first, Q = H_0 .. H_{n-1} takes it last */
+        const int j = transpose ? q : n - 1 - q;
+        const double t = tau[j];
+        if (t == 0.0) continue;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static) if ((int64_t)(m - j) * nrhs > 16384)
+#endif
+        for (int col = 0; col < nrhs; ++col) {
+            double s = b[j * pitch_b + col];
+            for (int i = j + 1; i < m; ++i) s += qr[i * pitch + j] * b[i * pitch_b + col];
+            s = t * s;
+            b[j * pitch_b + col] -= s;
+            for (int i = j + 1; i < m; ++i) b[i * pitch_b + col] -= qr[i * pitch + j] * s;
+        }
+    }
+}
+
+void mpx_cpu_qr_rsolve_f64(const double *qr, int n, int64_t pitch, double *b, int nrhs, int64_t pitch_b) {
+    if (!qr || !b || n <= 0 || nrhs <= 0 || pitch < n || pitch_b < nrhs) return;
+    for (int i = n - 1; i >= 0; --i) {
+        double *bi = b + i * pitch_b;
+        const double d = qr[i * pitch + i];
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static) if ((int64_t)(n - i) * nrhs > 16384)
+#endif
+        for (int j = 0; j < nrhs; ++j) {
+            double s = bi[j];
+            for (int k = i + 1; k < n; ++k) s -= qr[i * pitch + k] * b[k * pitch_b + j];
+            bi[j] = s / d;
+        }
+    }
+}

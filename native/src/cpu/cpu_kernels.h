@@ -63,6 +63,15 @@ void mpx_cpu_chol_solve_f64(const double *l, int n, int64_t pitch, double *b, in
 void mpx_cpu_chol_factor_batched_f64(double *a, int batch, int n, int64_t pitch, int64_t stride, int32_t *info);
 void mpx_cpu_chol_solve_batched_f64(const double *l, int batch, int n, int64_t pitch, int64_t stride, double *b,
                                     int nrhs, int64_t pitch_b, int64_t stride_b);
+/* lab4: unblocked Householder QR (m >= n, geqrf storage), the application of
+ * Q (transpose = 0) or Q^T from the stored reflectors and the solve with R,
+ * the contract of mpx_qr_factor_f64 / mpx_qr_apply_f64 / mpx_qr_rsolve_f64
+ * (capi.h): rows summed in ascending order, OpenMP over the columns of the
+ * update; bad arguments write nothing but *info = 0. */
+void mpx_cpu_qr_factor_f64(double *a, int m, int n, int64_t pitch, double *tau, int32_t *info);
+void mpx_cpu_qr_apply_f64(const double *qr, int m, int n, int64_t pitch, const double *tau, double *b, int nrhs,
+                          int64_t pitch_b, int transpose);
+void mpx_cpu_qr_rsolve_f64(const double *qr, int n, int64_t pitch, double *b, int nrhs, int64_t pitch_b);
 
 /* lab1 host text I/O (reference lab1/src/main.cu:46-52 scanf per value,
  * :82-84 printf per value), parallel over OpenMP threads in the -fopenmp builds
