@@ -58,6 +58,49 @@ def _pitch(a: torch.Tensor, width: int) -> int:
     return max(a.stride(0), width) if a.shape[0] > 1 else width
 
 
+def _b_layout(b: torch.Tensor, rows: int):
+    """``(nrhs, pitch_b)`` of a right-hand side solved in place: ``lu_solve_``'s stride rules."""
+    if b.dim() == 1:
+        if rows > 1 and b.stride(0) < 1:
+            raise ValueError("B must have a positive stride")
+        return 1, (max(b.stride(0), 1) if rows > 1 else 1)
+    nrhs = b.shape[1]
+    if nrhs and b.stride(1) != 1:
+        raise ValueError("B must have contiguous rows (stride(1) == 1)")
+    if rows > 1 and b.stride(0) < nrhs:
+        raise ValueError("B must have a row stride of at least its width")
+    return nrhs, _pitch(b, nrhs)
+
+
+def _check_rhs(b: torch.Tensor, rows: int, factors: torch.Tensor, what: str, *, in_place: bool = False,
+               letter: str = "n", owner: str | None = None, sized: bool = False, piv: torch.Tensor | None = None):
+    """The checks of a right-hand side ``b`` ((rows,) or (rows, k), float64, on
+    ``factors``' device; ``what`` is ``factors``' name in the messages).
+    ``in_place``: ``b`` is solved where it lies, so ``_b_layout``'s stride rules
+    hold too and ``(nrhs, pitch_b)`` is returned; the functions that work on a
+    contiguous copy take any strides. The rest only picks a wording: ``letter``
+    names the row count, ``owner`` the matrix of the row-count message where it
+    is not ``what``, ``sized`` is the wording of the functions that factor a
+    copy (one message with the sizes for dimension and row count), ``piv`` are
+    LU's pivots, which its device message names."""
+    if not isinstance(b, torch.Tensor) or b.dtype != torch.float64:
+        raise ValueError("B must be float64 (fp64 only)")
+    if sized:
+        if b.dim() not in (1, 2) or b.shape[0] != rows:
+            raise ValueError(f"B must be ({rows},) or ({rows}, k), not {tuple(b.shape)}")
+    else:
+        if b.dim() not in (1, 2):
+            raise ValueError(f"B must be ({letter},) or ({letter}, k), not {b.dim()}-D")
+        if b.shape[0] != rows:
+            raise ValueError(f"B has {b.shape[0]} rows, {owner or what} {rows}")
+    if piv is not None:
+        if piv.device != factors.device or b.device != factors.device:
+            raise ValueError(f"{what} is on {factors.device}, piv on {piv.device}, B on {b.device}")
+    elif b.device != factors.device:
+        raise ValueError(f"{what} is on {factors.device}, B on {b.device}")
+    return _b_layout(b, rows) if in_place else None
+
+
 def lu_factor_(a: torch.Tensor):
     """LU with partial pivoting of a square float64 matrix, in place. Rows must
     be contiguous; any row stride >= n is honoured as the pitch (a column slice
@@ -90,21 +133,13 @@ def lu_factor(a: torch.Tensor):
     return lu_factor_(a.clone(memory_format=torch.contiguous_format))
 
 
-def _check_solve(lu: torch.Tensor, piv: torch.Tensor, b: torch.Tensor) -> int:
+def _check_solve(lu: torch.Tensor, piv: torch.Tensor, b: torch.Tensor, in_place: bool = False):
     n = _check_matrix(lu, "LU")
     if not isinstance(piv, torch.Tensor) or piv.dtype != torch.int32 or piv.dim() != 1 or piv.shape[0] != n:
         raise ValueError(f"piv must be an int32 vector of {n} elements")
     if not piv.is_contiguous():
         raise ValueError("piv must be contiguous")
-    if not isinstance(b, torch.Tensor) or b.dtype != torch.float64:
-        raise ValueError("B must be float64 (fp64 only)")
-    if b.dim() not in (1, 2):
-        raise ValueError(f"B must be (n,) or (n, k), not {b.dim()}-D")
-    if b.shape[0] != n:
-        raise ValueError(f"B has {b.shape[0]} rows, LU {n}")
-    if piv.device != lu.device or b.device != lu.device:
-        raise ValueError(f"LU is on {lu.device}, piv on {piv.device}, B on {b.device}")
-    return n
+    return n, _check_rhs(b, n, lu, "LU", in_place=in_place, piv=piv)
 
 
 def lu_solve_(lu: torch.Tensor, piv: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -112,18 +147,7 @@ def lu_solve_(lu: torch.Tensor, piv: torch.Tensor, b: torch.Tensor) -> torch.Ten
     factors of ``lu_factor``: rows interchanged by ``piv``, forward substitution
     with unit L, back substitution with U. A 2-D ``b`` needs contiguous rows
     (any row stride >= k is the pitch); a 1-D ``b`` may have any stride."""
-    n = _check_solve(lu, piv, b)
-    if b.dim() == 1:
-        nrhs, pitch_b = 1, (max(b.stride(0), 1) if n > 1 else 1)
-        if n > 1 and b.stride(0) < 1:
-            raise ValueError("B must have a positive stride")
-    else:
-        nrhs = b.shape[1]
-        if nrhs and b.stride(1) != 1:
-            raise ValueError("B must have contiguous rows (stride(1) == 1)")
-        if n > 1 and b.stride(0) < nrhs:
-            raise ValueError("B must have a row stride of at least its width")
-        pitch_b = _pitch(b, nrhs)
+    n, (nrhs, pitch_b) = _check_solve(lu, piv, b, in_place=True)
     if n == 0 or nrhs == 0:
         return b
     L = _native.lib()
@@ -146,13 +170,7 @@ def solve(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """X with A X = B: factor a copy of ``a``, read ``info`` (the one host
     read), solve on a copy of ``b``. A singular matrix (an exactly zero pivot)
     raises ``RuntimeError`` naming the pivot's column."""
-    n = _check_matrix(a, "A")
-    if not isinstance(b, torch.Tensor) or b.dtype != torch.float64:
-        raise ValueError("B must be float64 (fp64 only)")
-    if b.dim() not in (1, 2) or b.shape[0] != n:
-        raise ValueError(f"B must be ({n},) or ({n}, k), not {tuple(b.shape)}")
-    if b.device != a.device:
-        raise ValueError(f"A is on {a.device}, B on {b.device}")
+    _check_rhs(b, _check_matrix(a, "A"), a, "A", sized=True)
     lu, piv, info = lu_factor(a)
     k = int(info.item())
     if k:
@@ -332,12 +350,7 @@ def solve_batched(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     ``info`` (the one host read), solve on a copy of ``b``. A singular member
     raises ``RuntimeError`` naming the first such batch index and its column."""
     batch, n, _, _ = _check_batch(a, "A")
-    if not isinstance(b, torch.Tensor) or b.dtype != torch.float64:
-        raise ValueError("B must be float64 (fp64 only)")
-    if b.dim() not in (2, 3) or b.shape[0] != batch or b.shape[1] != n:
-        raise ValueError(f"B must be ({batch}, {n}) or ({batch}, {n}, k), not {tuple(b.shape)}")
-    if b.device != a.device:
-        raise ValueError(f"A is on {a.device}, B on {b.device}")
+    _check_batch_b(b, a, "A", batch, n)
     lu, piv, info = lu_factor_batched(a)
     _raise_if_singular(info, "solve_batched")
     return lu_solve_batched(lu, piv, b)
@@ -405,17 +418,9 @@ def cholesky_factor(a: torch.Tensor):
     return cholesky_factor_(a.clone(memory_format=torch.contiguous_format))
 
 
-def _check_cholesky_solve(l: torch.Tensor, b: torch.Tensor) -> int:
+def _check_cholesky_solve(l: torch.Tensor, b: torch.Tensor, in_place: bool = False):
     n = _check_matrix(l, "L")
-    if not isinstance(b, torch.Tensor) or b.dtype != torch.float64:
-        raise ValueError("B must be float64 (fp64 only)")
-    if b.dim() not in (1, 2):
-        raise ValueError(f"B must be (n,) or (n, k), not {b.dim()}-D")
-    if b.shape[0] != n:
-        raise ValueError(f"B has {b.shape[0]} rows, L {n}")
-    if b.device != l.device:
-        raise ValueError(f"L is on {l.device}, B on {b.device}")
-    return n
+    return n, _check_rhs(b, n, l, "L", in_place=in_place)
 
 
 def cholesky_solve_(l: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -424,18 +429,7 @@ def cholesky_solve_(l: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     Lᵀ, both dividing by the diagonal; only L's lower triangle is read. ``b``
     has ``lu_solve_``'s stride rules: a 2-D ``b`` needs contiguous rows (any row
     stride >= k is the pitch), a 1-D ``b`` may have any positive stride."""
-    n = _check_cholesky_solve(l, b)
-    if b.dim() == 1:
-        nrhs, pitch_b = 1, (max(b.stride(0), 1) if n > 1 else 1)
-        if n > 1 and b.stride(0) < 1:
-            raise ValueError("B must have a positive stride")
-    else:
-        nrhs = b.shape[1]
-        if nrhs and b.stride(1) != 1:
-            raise ValueError("B must have contiguous rows (stride(1) == 1)")
-        if n > 1 and b.stride(0) < nrhs:
-            raise ValueError("B must have a row stride of at least its width")
-        pitch_b = _pitch(b, nrhs)
+    n, (nrhs, pitch_b) = _check_cholesky_solve(l, b, in_place=True)
     if n == 0 or nrhs == 0:
         return b
     L = _native.lib()
@@ -459,13 +453,7 @@ def solve_spd(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     what counts): factor a copy of ``a``, read ``info`` (the one host read),
     solve on a copy of ``b``. A matrix that is not positive definite raises
     ``RuntimeError`` naming the column where the factorisation broke down."""
-    n = _check_matrix(a, "A")
-    if not isinstance(b, torch.Tensor) or b.dtype != torch.float64:
-        raise ValueError("B must be float64 (fp64 only)")
-    if b.dim() not in (1, 2) or b.shape[0] != n:
-        raise ValueError(f"B must be ({n},) or ({n}, k), not {tuple(b.shape)}")
-    if b.device != a.device:
-        raise ValueError(f"A is on {a.device}, B on {b.device}")
+    _check_rhs(b, _check_matrix(a, "A"), a, "A", sized=True)
     l, info = cholesky_factor(a)
     k = int(info.item())
     if k:
@@ -603,20 +591,6 @@ def _check_tau(tau: torch.Tensor, qr: torch.Tensor, n: int) -> None:
         raise ValueError(f"QR is on {qr.device}, tau on {tau.device}")
 
 
-def _b_layout(b: torch.Tensor, rows: int):
-    """``(nrhs, pitch_b)`` of a right-hand side solved in place: ``lu_solve_``'s stride rules."""
-    if b.dim() == 1:
-        if rows > 1 and b.stride(0) < 1:
-            raise ValueError("B must have a positive stride")
-        return 1, (max(b.stride(0), 1) if rows > 1 else 1)
-    nrhs = b.shape[1]
-    if nrhs and b.stride(1) != 1:
-        raise ValueError("B must have contiguous rows (stride(1) == 1)")
-    if rows > 1 and b.stride(0) < nrhs:
-        raise ValueError("B must have a row stride of at least its width")
-    return nrhs, _pitch(b, nrhs)
-
-
 def qr_factor_(a: torch.Tensor):
     """Householder QR A = Q R of a float64 matrix with m >= n, in place, in
     LAPACK ``geqrf`` storage. Rows must be contiguous; any row stride >= n is
@@ -660,18 +634,10 @@ def qr_factor(a: torch.Tensor):
     return qr_factor_(a.clone(memory_format=torch.contiguous_format))
 
 
-def _check_mul_q(qr: torch.Tensor, tau: torch.Tensor, b: torch.Tensor):
+def _check_mul_q(qr: torch.Tensor, tau: torch.Tensor, b: torch.Tensor, in_place: bool = False):
     m, n = _check_tall(qr, "QR")
     _check_tau(tau, qr, n)
-    if not isinstance(b, torch.Tensor) or b.dtype != torch.float64:
-        raise ValueError("B must be float64 (fp64 only)")
-    if b.dim() not in (1, 2):
-        raise ValueError(f"B must be (m,) or (m, k), not {b.dim()}-D")
-    if b.shape[0] != m:
-        raise ValueError(f"B has {b.shape[0]} rows, QR {m}")
-    if b.device != qr.device:
-        raise ValueError(f"QR is on {qr.device}, B on {b.device}")
-    return m, n
+    return m, n, _check_rhs(b, m, qr, "QR", in_place=in_place, letter="m")
 
 
 def qr_mul_q_(qr: torch.Tensor, tau: torch.Tensor, b: torch.Tensor, transpose: bool = False) -> torch.Tensor:
@@ -680,8 +646,7 @@ def qr_mul_q_(qr: torch.Tensor, tau: torch.Tensor, b: torch.Tensor, transpose: b
     (four launches per 64 of them on the GPU; T is rebuilt, never stored). ``b``
     is (m,) or (m, k) float64 with ``lu_solve_``'s stride rules; its columns are
     independent."""
-    m, n = _check_mul_q(qr, tau, b)
-    nrhs, pitch_b = _b_layout(b, m)
+    m, n, (nrhs, pitch_b) = _check_mul_q(qr, tau, b, in_place=True)
     if m == 0 or n == 0 or nrhs == 0:
         return b
     L = _native.lib()
@@ -709,15 +674,7 @@ def qr_solve_r_(qr: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     triangle of ``qr[:n]``; ``b`` is (n,) or (n, k) with ``lu_solve_``'s stride
     rules. A zero on R's diagonal (``info`` of ``qr_factor``) divides by zero."""
     _, n = _check_tall(qr, "QR")
-    if not isinstance(b, torch.Tensor) or b.dtype != torch.float64:
-        raise ValueError("B must be float64 (fp64 only)")
-    if b.dim() not in (1, 2):
-        raise ValueError(f"B must be (n,) or (n, k), not {b.dim()}-D")
-    if b.shape[0] != n:
-        raise ValueError(f"B has {b.shape[0]} rows, R {n}")
-    if b.device != qr.device:
-        raise ValueError(f"QR is on {qr.device}, B on {b.device}")
-    nrhs, pitch_b = _b_layout(b, n)
+    nrhs, pitch_b = _check_rhs(b, n, qr, "QR", in_place=True, owner="R")
     if n == 0 or nrhs == 0:
         return b
     L = _native.lib()
@@ -747,12 +704,7 @@ def lstsq(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     ``R_jj``) raises ``RuntimeError`` naming the column. For m = n this is a
     linear solve."""
     m, n = _check_tall(a, "A")
-    if not isinstance(b, torch.Tensor) or b.dtype != torch.float64:
-        raise ValueError("B must be float64 (fp64 only)")
-    if b.dim() not in (1, 2) or b.shape[0] != m:
-        raise ValueError(f"B must be ({m},) or ({m}, k), not {tuple(b.shape)}")
-    if b.device != a.device:
-        raise ValueError(f"A is on {a.device}, B on {b.device}")
+    _check_rhs(b, m, a, "A", sized=True)
     qr, tau, info = qr_factor(a)
     k = int(info.item())
     if k:

@@ -8,8 +8,9 @@
 //   panel     chol_panel_kernel: L21 = A21 L11^-T, one lane per row, the rows
 //             staged through LDS with coalesced loads and stores, L11 in LDS
 //             read as broadcasts, k ascending as in the reference;
-//   update    chol_update_kernel<kSyrk>: A22 -= L21 L21^T on
-//             v_mfma_f64_16x16x4_f64, the T (T + 1) / 2 lower tiles only.
+//   update    chol_syrk_kernel: A22 -= L21 L21^T on v_mfma_f64_16x16x4_f64
+//             (dense_tile.hpp's tile, shared with lu.hip and qr.hip), the
+//             T (T + 1) / 2 lower tiles only.
 //
 // The factorisation launches diag once, for the first block. Every later
 // diagonal block is factored by the workgroup that has just updated it, tile
@@ -23,9 +24,9 @@
 // padding are never read or written.
 //
 // The solve is blocked forward (L y = b) and back (L^T x = y) substitution:
-// chol_trsm_kernel on the diagonal blocks, chol_update_kernel<kNN> / <kTN>
-// between them.
-#include "internal.hpp"
+// chol_trsm_kernel on the diagonal blocks, dense_tile.hpp's
+// dense_update_kernel<kRows> / <kKMajor> between them.
+#include "dense_tile.hpp"
 
 namespace mpx {
 MPX_MODULE_ANCHOR(chol)
@@ -33,8 +34,6 @@ MPX_MODULE_ANCHOR(chol)
 namespace {
 
 constexpr int NB = 64;  // panel width = K of the update
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 // The jb x jb block at (j0, j0), jb <= NB, by one workgroup, right-looking in
 // LDS: column j takes its square root and its divisions, then every element
@@ -250,179 +249,34 @@ __global__ __launch_bounds__(64) void chol_trsm_kernel(const double *__restrict_
     for (int i = 0; i < jb; ++i) b[(int64_t)i * ldb + col] = xs[xs_at(i, tid)];
 }
 
-// The two LDS layouts of a 64 x 64 MFMA operand block, both filled with
-// coalesced global reads and vector LDS stores, both read without conflicts:
-//   rows    X[r][k ^ ((r & 15) << 1)] from a matrix whose rows hold k contiguously;
-//           an operand read X[base + (l & 15)][4 t + (l >> 4)] then takes 32 distinct
-//           bank pairs per half-wave: bit 0 from l >> 4, bits 1..4 from l & 15
-//           (lu_update_kernel's << 2 leaves rows r and r + 8 on the same pairs:
-//           8 conflict cycles per LDS instruction on the counters, 0 with << 1);
-//   kmajor  X[k][c ^ ((k & 3) << 4)] from a matrix whose rows hold c contiguously;
-//           the four k rows of an operand read take distinct segments.
-// An operand uses the layout its global storage has, so nothing is transposed on
-// the way into LDS: the update of the factorisation reads L21 twice as `rows`
-// (its B operand B[k][c] = L21[n0 + c][k] is the A read of other rows), the
-// backward update reads L^T's block as `kmajor`.
-// Zero-filled outside [0, rmax) x [0, kmax); NEG stages the negative.
-template <bool V2, bool NEG>
-__device__ __forceinline__ void stage_rows(double *__restrict__ dst, const double *__restrict__ src, int64_t ld,
-                                           int rmax, int kmax, int tid) {
-    if (V2) {
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int e = tid + it * 256;
-            const int r = e >> 5, k = (e & 31) * 2;
-            double2 v = {0.0, 0.0};
-            if (r < rmax) {
-                const double *p = src + (int64_t)r * ld + k;
-                if (k + 1 < kmax)
-                    v = *reinterpret_cast<const double2 *>(p);
-                else if (k < kmax)
-                    v.x = *p;
-            }
-            if (NEG) v = double2{-v.x, -v.y};
-            *reinterpret_cast<double2 *>(&dst[r * 64 + (k ^ ((r & 15) << 1))]) = v;
-        }
-    } else {
-#pragma unroll
-        for (int it = 0; it < 16; ++it) {
-            const int e = tid + it * 256;
-            const int r = e >> 6, k = e & 63;
-            const double v = (r < rmax && k < kmax) ? src[(int64_t)r * ld + k] : 0.0;
-            dst[r * 64 + (k ^ ((r & 15) << 1))] = NEG ? -v : v;
-        }
-    }
-}
-
-template <bool V2, bool NEG>
-__device__ __forceinline__ void stage_kmajor(double *__restrict__ dst, const double *__restrict__ src, int64_t ld,
-                                             int kmax, int cmax, int tid) {
-    if (V2) {
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int e = tid + it * 256;
-            const int k = e >> 5, c = (e & 31) * 2;
-            double2 v = {0.0, 0.0};
-            if (k < kmax) {
-                const double *p = src + (int64_t)k * ld + c;
-                if (c + 1 < cmax)
-                    v = *reinterpret_cast<const double2 *>(p);
-                else if (c < cmax)
-                    v.x = *p;
-            }
-            if (NEG) v = double2{-v.x, -v.y};
-            *reinterpret_cast<double2 *>(&dst[k * 64 + (c ^ ((k & 3) << 4))]) = v;
-        }
-    } else {
-#pragma unroll
-        for (int it = 0; it < 16; ++it) {
-            const int e = tid + it * 256;
-            const int k = e >> 6, c = e & 63;
-            const double v = (k < kmax && c < cmax) ? src[(int64_t)k * ld + c] : 0.0;
-            dst[k * 64 + (c ^ ((k & 3) << 4))] = NEG ? -v : v;
-        }
-    }
-}
-
-enum UpdateMode {
-    kNN = 0,    // C (M x N) -= A (M x K) B (K x N)
-    kTN = 1,    // C (M x N) -= A^T B, A stored K x M
-    kSyrk = 2,  // C (M x M), col <= row only, -= A A^T, A stored M x K; B is ignored
-};
-
-// K <= NB. A workgroup owns a 64 x 64 tile of C: it stages -A and B in LDS once,
-// each of its four waves takes a 32 x 32 quarter as 2 x 2 MFMA tiles with C
-// loaded into the accumulators, and stores them predicated.
-//   A operand: lane l holds A[l & 15][4 t + (l >> 4)], B: B[4 t + (l >> 4)][l & 15],
-//   C/D: lane l, reg r holds row (l >> 4) + 4 r, column l & 15 (the f64 map).
-// kSyrk: blockIdx.x counts the lower tiles row by row, (bi, bj) with bj <= bi;
+// A22 (M x M, col <= row only) -= A A^T, A = L21 stored M x K, K <= NB, on
+// dense_tile.hpp's tile: both operands are row blocks of A in the `rows` layout.
+// blockIdx.x counts the lower tiles row by row, (bi, bj) with bj <= bi;
 // diagonal tiles touch C only where col <= row, and their upper-right wave has
 // nothing to do.
-// V2: 16-byte global loads (16-byte aligned operands with even pitches).
-// AHEAD (kSyrk): the workgroup of tile (0, 0) goes on to factor that tile, the
-// next panel's diagonal block at column jn (diag_block, the same code and so the
-// same bits as chol_diag_kernel), while the other tiles are still being updated:
-// the block's serial 64 columns leave the critical path and the next panel
-// needs no launch for them. Nobody waits on anybody: the tile is this
-// workgroup's own.
-template <int MODE, bool V2, bool AHEAD>
-__global__ __launch_bounds__(256) void chol_update_kernel(const double *__restrict__ A, int64_t lda,
-                                                          const double *__restrict__ B, int64_t ldb, double *C,
-                                                          int64_t ldc, int M, int N, int K, int jn, int32_t *info) {
+// V2: 16-byte global loads (a 16-byte aligned A with an even pitch).
+// AHEAD: the workgroup of tile (0, 0) goes on to factor that tile, the next
+// panel's diagonal block at column jn (diag_block, the same code and so the same
+// bits as chol_diag_kernel), while the other tiles are still being updated: the
+// block's serial 64 columns leave the critical path and the next panel needs no
+// launch for them. Nobody waits on anybody: the tile is this workgroup's own.
+template <bool V2, bool AHEAD>
+__global__ __launch_bounds__(256) void chol_syrk_kernel(const double *__restrict__ A, int64_t lda, double *C,
+                                                        int64_t ldc, int M, int K, int jn, int32_t *info) {
     __shared__ __attribute__((aligned(16))) double lds[2 * NB * 64];
     static_assert(sizeof(double) * (NB + 1) * NB <= sizeof(lds), "diag_block's tile fits the operands' LDS");
     double *As = lds, *Bs = lds + NB * 64;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int bi = blockIdx.y, bj = blockIdx.x;
-    if (MODE == kSyrk) {
-        const int b = blockIdx.x;
-        bi = (int)((sqrtf(8.0f * (float)b + 1.0f) - 1.0f) * 0.5f);
-        while ((bi + 1) * (bi + 2) / 2 <= b) ++bi;
-        while (bi * (bi + 1) / 2 > b) --bi;
-        bj = b - bi * (bi + 1) / 2;
-    }
+    const int tid = threadIdx.x, wave = tid >> 6;
+    const int b = blockIdx.x;
+    int bi = (int)((sqrtf(8.0f * (float)b + 1.0f) - 1.0f) * 0.5f);
+    while ((bi + 1) * (bi + 2) / 2 <= b) ++bi;
+    while (bi * (bi + 1) / 2 > b) --bi;
+    const int bj = b - bi * (bi + 1) / 2;
     const int m0 = bi * 64, n0 = bj * 64;
-    if (MODE == kTN)
-        stage_kmajor<V2, true>(As, A + m0, lda, K, M - m0, tid);
-    else
-        stage_rows<V2, true>(As, A + (int64_t)m0 * lda, lda, M - m0, K, tid);
-    if (MODE == kSyrk)
-        stage_rows<V2, false>(Bs, A + (int64_t)n0 * lda, lda, M - n0, K, tid);
-    else
-        stage_kmajor<V2, false>(Bs, B + n0, ldb, K, N - n0, tid);
-    const int g = lane >> 4, l15 = lane & 15;
-    const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
-    const bool idle = MODE == kSyrk && bi == bj && wc > wr;  // wave-uniform
-    f64x4 acc[2][2];
-#pragma unroll
-    for (int im = 0; im < 2; ++im)
-#pragma unroll
-        for (int in = 0; in < 2; ++in)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = m0 + wr + im * 16 + g + 4 * r, col = n0 + wc + in * 16 + l15;
-                const bool in_c = MODE == kSyrk ? (row < M && col <= row) : (row < M && col < N);
-                acc[im][in][r] = in_c ? C[(int64_t)row * ldc + col] : 0.0;
-            }
-    __syncthreads();
-    if (!idle) {
-    for (int k0 = 0; k0 < K; k0 += 16) {  // uniform: a ragged solve block stops early
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int k = k0 + 4 * t + g;
-            const int kr = k ^ (l15 << 1);
-            double a0, a1, b0, b1;
-            if (MODE == kTN) {
-                a0 = As[k * 64 + ((wr + l15) ^ (g << 4))];
-                a1 = As[k * 64 + ((wr + 16 + l15) ^ (g << 4))];
-            } else {
-                a0 = As[(wr + l15) * 64 + kr];
-                a1 = As[(wr + 16 + l15) * 64 + kr];
-            }
-            if (MODE == kSyrk) {
-                b0 = Bs[(wc + l15) * 64 + kr];
-                b1 = Bs[(wc + 16 + l15) * 64 + kr];
-            } else {
-                b0 = Bs[k * 64 + ((wc + l15) ^ (g << 4))];
-                b1 = Bs[k * 64 + ((wc + 16 + l15) ^ (g << 4))];
-            }
-            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int im = 0; im < 2; ++im)
-#pragma unroll
-        for (int in = 0; in < 2; ++in)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = m0 + wr + im * 16 + g + 4 * r, col = n0 + wc + in * 16 + l15;
-                const bool in_c = MODE == kSyrk ? (row < M && col <= row) : (row < M && col < N);
-                if (in_c) C[(int64_t)row * ldc + col] = acc[im][in][r];
-            }
-    }
+    stage_rows<V2, true>(As, A + (int64_t)m0 * lda, lda, M - m0, K, tid);
+    stage_rows<V2, false>(Bs, A + (int64_t)n0 * lda, lda, M - n0, K, tid);
+    const bool idle = bi == bj && (wave & 1) > (wave >> 1);  // wave-uniform: the quarter above the diagonal
+    tile_update<true, kRows, kRows>(C, ldc, m0, n0, M, M, As, Bs, K, idle);
     if (AHEAD && blockIdx.x == 0) {
         __threadfence_block();
         __syncthreads();  // the tile is in memory for this workgroup, and the operands' LDS is free
@@ -430,19 +284,16 @@ __global__ __launch_bounds__(256) void chol_update_kernel(const double *__restri
     }
 }
 
-template <int MODE, bool AHEAD = false>
-int launch_update(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int M, int N,
-                  int K, hipStream_t s, int jn = 0, int32_t *info = nullptr) {
-    if (M <= 0 || N <= 0 || K <= 0) return MPX_OK;
-    const int tm = (M + 63) / 64, tn = (N + 63) / 64;
-    const dim3 grid = MODE == kSyrk ? dim3(tm * (tm + 1) / 2) : dim3(tn, tm);
-    const bool v2 = aligned16(A) && lda % 2 == 0 && (MODE == kSyrk || (aligned16(B) && ldb % 2 == 0));
-    if (v2)
-        hipLaunchKernelGGL((chol_update_kernel<MODE, true, AHEAD>), grid, dim3(256), 0, s, A, lda, B, ldb, C, ldc, M,
-                           N, K, jn, info);
+template <bool AHEAD = false>
+int launch_syrk(const double *A, int64_t lda, double *C, int64_t ldc, int M, int K, hipStream_t s, int jn = 0,
+                int32_t *info = nullptr) {
+    if (M <= 0 || K <= 0) return MPX_OK;
+    const int tm = (M + 63) / 64;
+    const dim3 grid(tm * (tm + 1) / 2);
+    if (aligned16(A) && lda % 2 == 0)
+        hipLaunchKernelGGL((chol_syrk_kernel<true, AHEAD>), grid, dim3(256), 0, s, A, lda, C, ldc, M, K, jn, info);
     else
-        hipLaunchKernelGGL((chol_update_kernel<MODE, false, AHEAD>), grid, dim3(256), 0, s, A, lda, B, ldb, C, ldc, M,
-                           N, K, jn, info);
+        hipLaunchKernelGGL((chol_syrk_kernel<false, AHEAD>), grid, dim3(256), 0, s, A, lda, C, ldc, M, K, jn, info);
     MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
     return MPX_OK;
 }
@@ -473,8 +324,8 @@ int panel_step(double *a, int n, int64_t pitch, int32_t *info, int j0, int mask,
         MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
     }
     if (mask & 4) {
-        if (ahead) return launch_update<kSyrk, true>(a21, pitch, nullptr, 0, a21 + jb, pitch, rest, rest, jb, s, j0 + jb, info);
-        return launch_update<kSyrk>(a21, pitch, nullptr, 0, a21 + jb, pitch, rest, rest, jb, s);
+        if (ahead) return launch_syrk<true>(a21, pitch, a21 + jb, pitch, rest, jb, s, j0 + jb, info);
+        return launch_syrk(a21, pitch, a21 + jb, pitch, rest, jb, s);
     }
     return MPX_OK;
 }
@@ -519,8 +370,8 @@ extern "C" int mpx_chol_solve_f64(const double *l, int n, int64_t pitch, double 
         const double *t = l + (int64_t)k0 * pitch + k0;
         double *bk = b + (int64_t)k0 * pitch_b;
         if (int rc = launch_trsm<false>(t, pitch, jb, bk, pitch_b, nrhs, s)) return rc;
-        if (int rc = launch_update<kNN>(t + (int64_t)jb * pitch, pitch, bk, pitch_b, bk + (int64_t)jb * pitch_b,
-                                        pitch_b, n - k0 - jb, nrhs, jb, s))
+        if (int rc = launch_dense_update<kRows>(t + (int64_t)jb * pitch, pitch, bk, pitch_b,
+                                                bk + (int64_t)jb * pitch_b, pitch_b, n - k0 - jb, nrhs, jb, s))
             return rc;
     }
     for (int k0 = (n - 1) / NB * NB; k0 >= 0; k0 -= NB) {  // L^T x = y
@@ -528,7 +379,7 @@ extern "C" int mpx_chol_solve_f64(const double *l, int n, int64_t pitch, double 
         const double *lk = l + (int64_t)k0 * pitch;
         double *bk = b + (int64_t)k0 * pitch_b;
         if (int rc = launch_trsm<true>(lk + k0, pitch, jb, bk, pitch_b, nrhs, s)) return rc;
-        if (int rc = launch_update<kTN>(lk, pitch, bk, pitch_b, b, pitch_b, k0, nrhs, jb, s)) return rc;
+        if (int rc = launch_dense_update<kKMajor>(lk, pitch, bk, pitch_b, b, pitch_b, k0, nrhs, jb, s)) return rc;
     }
     return MPX_OK;
 }

@@ -12,16 +12,19 @@
 //             that size is one launch plus the init);
 //   laswp     lu_laswp_kernel: the panel's interchanges left and right of it,
 //             in order (they do not commute), one lane per column;
-//   U12       lu_trsm_kernel<false>: one lane per column, the unit triangle in
+//   U12       dense_trsm_kernel<false>: one lane per column, the unit triangle in
 //             LDS read as broadcasts, substitution down the column in registers;
-//   update    lu_update_kernel: C -= A B for K <= 64 on v_mfma_f64_16x16x4_f64,
-//             both operands staged once in LDS (no K loop to pipeline).
+//   update    dense_update_kernel<kRows>: C -= A B for K <= 64 on
+//             v_mfma_f64_16x16x4_f64, both operands staged once in LDS.
 //
 // The solve permutes B, then runs blocked forward / back substitution with
-// lu_trsm_kernel on the diagonal blocks and lu_update_kernel between them.
+// dense_trsm_kernel on the diagonal blocks and dense_update_kernel between
+// them. Both kernels, the tile they are built from, the init kernel and the
+// panel-column kernel's handshake are dense_tile.hpp's, shared with chol.hip and
+// qr.hip.
 #include <climits>
 
-#include "internal.hpp"
+#include "dense_tile.hpp"
 
 namespace mpx {
 MPX_MODULE_ANCHOR(lu)
@@ -39,8 +42,6 @@ struct PivPart {  // a partial pivot search: largest |a_ik| and its lowest row
     int pad;
 };
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
 // the pivot rule: larger magnitude, the lower row among equal ones (NaN never wins)
 __device__ __forceinline__ void take_better(double &bv, int &bi, double v, int i) {
     if (v > bv || (v == bv && i < bi)) {
@@ -56,11 +57,6 @@ __device__ __forceinline__ void wave_best(double &v, int &i) {
         const int oi = __shfl_xor(i, s);
         take_better(v, i, ov, oi);
     }
-}
-
-__global__ void lu_init_kernel(int32_t *info, unsigned *counter) {
-    *info = 0;
-    *counter = 0;
 }
 
 // Panel [j0, j0 + jb) at step j (-1: only the pivot search of column j0). With
@@ -110,13 +106,8 @@ __global__ __launch_bounds__(256) void lu_panel_col_kernel(double *__restrict__ 
     // one partial per wave, written by the lane that owns column cn, so that a
     // single fence covers the rows and the partial
     if (lane == cn - j0) part[blockIdx.x * 4 + wave] = PivPart{bv, bi, 0};
-    __threadfence();  // this thread's stores before the counter below
-    __syncthreads();
-    if (threadIdx.x == 0) s_flag = atomicAdd(counter, 1u) == gridDim.x - 1;
-    __syncthreads();
-    if (!s_flag) return;
+    if (!last_workgroup(counter, &s_flag)) return;
     // the last workgroup to finish: every other one's rows and partials are visible
-    __threadfence();
     double *rc = a + (int64_t)cn * pitch + col;
     const double t0 = threadIdx.x < jb ? *rc : 0.0;  // in flight while the partials are folded
     bv = -1.0;
@@ -230,165 +221,6 @@ __global__ __launch_bounds__(64) void lu_permute_kernel(double *__restrict__ b, 
     }
 }
 
-// B (jb x ncols) <- T^-1 B by substitution, T the jb x jb (jb <= NB) block at t:
-// its strict lower part with a unit diagonal, or its upper part. T sits in LDS
-// and is read as broadcasts; a lane owns a column of B, which it keeps in its
-// own LDS column (64 doubles in registers with the loops unrolled spilled).
-template <bool UPPER>
-__global__ __launch_bounds__(64) void lu_trsm_kernel(const double *__restrict__ t, int64_t ldt, int jb,
-                                                     double *__restrict__ b, int64_t ldb, int ncols) {
-    __shared__ double s[NB][NB];
-    __shared__ double xs[NB][64];
-    const int tid = threadIdx.x;
-    for (int e = tid; e < NB * NB; e += 64) {
-        const int i = e >> 6, k = e & 63;
-        if (i < jb && k < jb) s[i][k] = t[(int64_t)i * ldt + k];
-    }
-    const int col = blockIdx.x * 64 + tid;
-    const bool ok = col < ncols;
-#pragma unroll 8
-    for (int i = 0; i < jb; ++i) xs[i][tid] = ok ? b[(int64_t)i * ldb + col] : 0.0;
-    __syncthreads();
-    if (!UPPER) {
-        for (int i = 1; i < jb; ++i) {
-            double acc = xs[i][tid];
-#pragma unroll 4
-            for (int k = 0; k < i; ++k) acc -= s[i][k] * xs[k][tid];
-            xs[i][tid] = acc;
-        }
-    } else {
-        for (int i = jb - 1; i >= 0; --i) {
-            double acc = xs[i][tid];
-#pragma unroll 4
-            for (int k = i + 1; k < jb; ++k) acc -= s[i][k] * xs[k][tid];
-            xs[i][tid] = acc / s[i][i];
-        }
-    }
-    if (!ok) return;
-#pragma unroll 8
-    for (int i = 0; i < jb; ++i) b[(int64_t)i * ldb + col] = xs[i][tid];
-}
-
-// C (M x N) -= A (M x K) B (K x N), K <= NB. A workgroup owns a 64 x 64 tile of
-// C: it stages -A (64 x 64) and B (64 x 64) in LDS once, zero-filled past M, N
-// and K, each of its four waves takes a 32 x 32 quarter as 2 x 2 MFMA tiles with
-// C loaded into the accumulators, and stores them predicated.
-//   A operand: lane l holds A[l & 15][4 t + (l >> 4)], B: B[4 t + (l >> 4)][l & 15],
-//   C/D: lane l, reg r holds row (l >> 4) + 4 r, column l & 15 (the f64 map).
-// LDS swizzles (both keep even / odd pairs adjacent for the 16-byte stores):
-//   As[r][k ^ ((r & 15) << 2)]: the 16 rows of an A read spread over all banks,
-//   Bs[k][c ^ ((k & 3) << 4)]: the four k rows of a B read take distinct segments.
-// V2: 16-byte global loads (16-byte aligned A and B with even pitches).
-template <bool V2>
-__global__ __launch_bounds__(256) void lu_update_kernel(const double *__restrict__ A, int64_t lda,
-                                                        const double *__restrict__ B, int64_t ldb, double *C,
-                                                        int64_t ldc, int M, int N, int K) {
-    __shared__ __attribute__((aligned(16))) double As[NB * 64];
-    __shared__ __attribute__((aligned(16))) double Bs[NB * 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
-    if (V2) {
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int e = tid + it * 256;
-            const int r = e >> 5, k = (e & 31) * 2;
-            double2 v = {0.0, 0.0};
-            if (m0 + r < M) {
-                const double *src = A + (int64_t)(m0 + r) * lda + k;
-                if (k + 1 < K)
-                    v = *reinterpret_cast<const double2 *>(src);
-                else if (k < K)
-                    v.x = *src;
-            }
-            *reinterpret_cast<double2 *>(&As[r * 64 + (k ^ ((r & 15) << 2))]) = double2{-v.x, -v.y};
-        }
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int e = tid + it * 256;
-            const int k = e >> 5, c = (e & 31) * 2;
-            double2 v = {0.0, 0.0};
-            if (k < K) {
-                const double *src = B + (int64_t)k * ldb + n0 + c;
-                if (n0 + c + 1 < N)
-                    v = *reinterpret_cast<const double2 *>(src);
-                else if (n0 + c < N)
-                    v.x = *src;
-            }
-            *reinterpret_cast<double2 *>(&Bs[k * 64 + (c ^ ((k & 3) << 4))]) = v;
-        }
-    } else {
-#pragma unroll
-        for (int it = 0; it < 16; ++it) {
-            const int e = tid + it * 256;
-            const int r = e >> 6, k = e & 63;
-            const double v = (m0 + r < M && k < K) ? A[(int64_t)(m0 + r) * lda + k] : 0.0;
-            As[r * 64 + (k ^ ((r & 15) << 2))] = -v;
-        }
-#pragma unroll
-        for (int it = 0; it < 16; ++it) {
-            const int e = tid + it * 256;
-            const int k = e >> 6, c = e & 63;
-            const double v = (k < K && n0 + c < N) ? B[(int64_t)k * ldb + n0 + c] : 0.0;
-            Bs[k * 64 + (c ^ ((k & 3) << 4))] = v;
-        }
-    }
-    const int g = lane >> 4, l15 = lane & 15;
-    const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
-    f64x4 acc[2][2];
-#pragma unroll
-    for (int im = 0; im < 2; ++im)
-#pragma unroll
-        for (int in = 0; in < 2; ++in)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = m0 + wr + im * 16 + g + 4 * r, col = n0 + wc + in * 16 + l15;
-                acc[im][in][r] = (row < M && col < N) ? C[(int64_t)row * ldc + col] : 0.0;
-            }
-    __syncthreads();
-    for (int k0 = 0; k0 < K; k0 += 16) {  // uniform: a narrower K (a tuning panel, a ragged solve block) stops early
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int k = k0 + 4 * t + g;
-            const int ka = k ^ (l15 << 2);
-            const double a0 = As[(wr + l15) * 64 + ka], a1 = As[(wr + 16 + l15) * 64 + ka];
-            const double b0 = Bs[k * 64 + ((wc + l15) ^ (g << 4))], b1 = Bs[k * 64 + ((wc + 16 + l15) ^ (g << 4))];
-            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int im = 0; im < 2; ++im)
-#pragma unroll
-        for (int in = 0; in < 2; ++in)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = m0 + wr + im * 16 + g + 4 * r, col = n0 + wc + in * 16 + l15;
-                if (row < M && col < N) C[(int64_t)row * ldc + col] = acc[im][in][r];
-            }
-}
-
-int launch_update(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int M, int N,
-                  int K, hipStream_t s) {
-    if (M <= 0 || N <= 0 || K <= 0) return MPX_OK;
-    const dim3 grid((N + 63) / 64, (M + 63) / 64);
-    if (aligned16(A) && aligned16(B) && lda % 2 == 0 && ldb % 2 == 0)
-        hipLaunchKernelGGL(lu_update_kernel<true>, grid, dim3(256), 0, s, A, lda, B, ldb, C, ldc, M, N, K);
-    else
-        hipLaunchKernelGGL(lu_update_kernel<false>, grid, dim3(256), 0, s, A, lda, B, ldb, C, ldc, M, N, K);
-    MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
-    return MPX_OK;
-}
-
-template <bool UPPER>
-int launch_trsm(const double *t, int64_t ldt, int jb, double *b, int64_t ldb, int ncols, hipStream_t s) {
-    if (ncols <= 0 || jb <= 0) return MPX_OK;
-    hipLaunchKernelGGL(lu_trsm_kernel<UPPER>, dim3((ncols + 63) / 64), dim3(64), 0, s, t, ldt, jb, b, ldb, ncols);
-    MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
-    return MPX_OK;
-}
-
 int launch_laswp(double *a, int n, int64_t pitch, int k0, int k1, const int32_t *piv, int cl, int cr, hipStream_t s) {
     const int cols = cl + (n - cr);
     if (cols <= 0) return MPX_OK;
@@ -435,10 +267,10 @@ int panel_step(double *a, int n, int64_t pitch, int32_t *piv, int32_t *info, int
     if (mask & 2)
         if (int rc = launch_laswp(a, n, pitch, j0, j0 + NB, piv, j0, j0 + NB, s)) return rc;
     if (mask & 4)
-        if (int rc = launch_trsm<false>(ajj, pitch, NB, ajj + NB, pitch, rest, s)) return rc;
+        if (int rc = launch_dense_trsm<false>(ajj, pitch, NB, ajj + NB, pitch, rest, s)) return rc;
     if (mask & 8)
-        if (int rc = launch_update(ajj + (int64_t)NB * pitch, pitch, ajj + NB, pitch, ajj + (int64_t)NB * pitch + NB,
-                                   pitch, rest, rest, NB, s))
+        if (int rc = launch_dense_update<kRows>(ajj + (int64_t)NB * pitch, pitch, ajj + NB, pitch,
+                                                ajj + (int64_t)NB * pitch + NB, pitch, rest, rest, NB, s))
             return rc;
     return MPX_OK;
 }
@@ -474,7 +306,7 @@ extern "C" int mpx_lu_factor_f64(double *a, int n, int64_t pitch, int32_t *piv, 
     if (n == 0) return MPX_OK;
     hipStream_t s = as_stream(stream);
     const Ws ws = ws_of(workspace);
-    hipLaunchKernelGGL(lu_init_kernel, dim3(1), dim3(1), 0, s, info, ws.counter);
+    hipLaunchKernelGGL(dense_init_kernel<>, dim3(1), dim3(1), 0, s, info, ws.counter);
     MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
     int j0 = 0;
     for (; n - j0 > kTailRows; j0 += panel_nb())
@@ -491,7 +323,7 @@ extern "C" int mpx_lu_phase_f64(double *a, int n, int64_t pitch, int32_t *piv, i
     MPX_CHECK_ARG(phase >= 0 && phase < 4, "lu: phase outside 0..3");
     const Ws ws = ws_of(workspace);
     if (phase == 0) {
-        hipLaunchKernelGGL(lu_init_kernel, dim3(1), dim3(1), 0, as_stream(stream), info, ws.counter);
+        hipLaunchKernelGGL(dense_init_kernel<>, dim3(1), dim3(1), 0, as_stream(stream), info, ws.counter);
         MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
     }
     return panel_step(a, n, pitch, piv, info, j0, 1 << phase, ws, as_stream(stream));
@@ -512,16 +344,16 @@ extern "C" int mpx_lu_solve_f64(const double *lu, int n, int64_t pitch, const in
         const int jb = n - k0 < NB ? n - k0 : NB;
         const double *t = lu + (int64_t)k0 * pitch + k0;
         double *bk = b + (int64_t)k0 * pitch_b;
-        if (int rc = launch_trsm<false>(t, pitch, jb, bk, pitch_b, nrhs, s)) return rc;
-        if (int rc = launch_update(t + (int64_t)jb * pitch, pitch, bk, pitch_b, bk + (int64_t)jb * pitch_b, pitch_b,
-                                   n - k0 - jb, nrhs, jb, s))
+        if (int rc = launch_dense_trsm<false>(t, pitch, jb, bk, pitch_b, nrhs, s)) return rc;
+        if (int rc = launch_dense_update<kRows>(t + (int64_t)jb * pitch, pitch, bk, pitch_b,
+                                                bk + (int64_t)jb * pitch_b, pitch_b, n - k0 - jb, nrhs, jb, s))
             return rc;
     }
     for (int k0 = (n - 1) / NB * NB; k0 >= 0; k0 -= NB) {  // U x = y
         const int jb = n - k0 < NB ? n - k0 : NB;
         double *bk = b + (int64_t)k0 * pitch_b;
-        if (int rc = launch_trsm<true>(lu + (int64_t)k0 * pitch + k0, pitch, jb, bk, pitch_b, nrhs, s)) return rc;
-        if (int rc = launch_update(lu + k0, pitch, bk, pitch_b, b, pitch_b, k0, nrhs, jb, s)) return rc;
+        if (int rc = launch_dense_trsm<true>(lu + (int64_t)k0 * pitch + k0, pitch, jb, bk, pitch_b, nrhs, s)) return rc;
+        if (int rc = launch_dense_update<kRows>(lu + k0, pitch, bk, pitch_b, b, pitch_b, k0, nrhs, jb, s)) return rc;
     }
     return MPX_OK;
 }

@@ -21,7 +21,8 @@
 //             forward, columnwise), one workgroup;
 //   Z         qr_z_kernel: the chunks of W summed in order, Z = T^T W (or T W
 //             for Q), lane = column;
-//   apply     qr_update_kernel: C -= V Z, K = 64, both operands staged once.
+//   apply     dense_update_kernel<kRows, ., true>: C -= V Z, K = 64, both
+//             operands staged once, V's diagonal block masked the same way.
 //
 // A factorisation is n + ceil(n / 64) panel launches, four more per panel that
 // has columns to its right, and one init: n + O(n / 64). An application of Q or
@@ -30,9 +31,11 @@
 // workgroup follow from m and the column's index alone, so column j of the
 // result is a function of columns 0 .. j.
 //
-// rsolve is blocked back substitution with R: qr_trsm_kernel on the diagonal
-// blocks, qr_update_kernel between them.
-#include "internal.hpp"
+// rsolve is blocked back substitution with R: dense_trsm_kernel<true> on the
+// diagonal blocks, dense_update_kernel between them. The MFMA tile with its LDS
+// layouts, these two kernels, the init kernel and the panel kernel's handshake
+// are dense_tile.hpp's, shared with lu.hip and chol.hip.
+#include "dense_tile.hpp"
 
 namespace mpx {
 MPX_MODULE_ANCHOR(qr)
@@ -43,18 +46,10 @@ constexpr int NB = 64;             // panel width = K of the apply
 constexpr int kChunkRows = 1024;   // rows of one partial W (16 K steps of 64)
 constexpr int kWsHeader = 256;     // bytes in front: word 0 = the finished-workgroup counter
 constexpr int kStateDoubles = 128; // w[64] of the pending rank-1 update, [64] = alpha - beta (0: none)
-constexpr int kNoUnit = 1 << 30;   // "this block is not the panel's diagonal block"
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 // rows per workgroup of the panel kernel: 64, more for very tall matrices so
 // that the fold stays within 256 partials; a function of m alone
 int panel_rows(int m) { return 64 * (m > 16384 ? (m + 16383) / 16384 : 1); }
-
-__global__ void qr_init_kernel(int32_t *info, unsigned *counter) {
-    *info = 0;
-    *counter = 0;
-}
 
 // Panel [j0, j0 + jb), launch j in 0 .. jb, c = j0 + j; lane = panel column.
 // Rows i >= c: with the pending reflector c - 1 (state: w, d = alpha - beta,
@@ -108,13 +103,8 @@ __global__ __launch_bounds__(256) void qr_panel_col_kernel(double *a, int m, int
     s_g[wave][lane] = g;
     __syncthreads();
     if (wave == 0) part[(int64_t)blockIdx.x * 64 + lane] = ((s_g[0][lane] + s_g[1][lane]) + s_g[2][lane]) + s_g[3][lane];
-    __threadfence();  // this thread's stores before the counter below
-    __syncthreads();
-    if (threadIdx.x == 0) s_flag = atomicAdd(counter, 1u) == gridDim.x - 1;
-    __syncthreads();
-    if (!s_flag) return;
+    if (!last_workgroup(counter, &s_flag)) return;
     // the last workgroup to finish: every other one's rows and partials are visible
-    __threadfence();
     double acc = 0.0;
     for (int b = wave; b < (int)gridDim.x; b += 4) acc += part[(int64_t)b * 64 + lane];
     s_g[wave][lane] = acc;
@@ -145,93 +135,14 @@ __global__ __launch_bounds__(256) void qr_panel_col_kernel(double *a, int m, int
     }
 }
 
-// The two LDS layouts of a 64 x 64 MFMA operand block (chol.hip's, with its
-// swizzles), zero-filled outside [0, rmax) x [0, kmax) resp. [0, kmax) x [0, cmax).
-// `unit` is the index of the block's first row within the panel's V, or
-// kNoUnit: rows below 64 of V are the panel's diagonal block, which holds R on
-// and above its diagonal and stands for a unit lower triangle.
-__device__ __forceinline__ double unit_lower(double v, int row, int col) {
-    return row >= NB || row > col ? v : (row == col ? 1.0 : 0.0);
-}
-
-template <bool V2, bool NEG>
-__device__ __forceinline__ void stage_rows(double *__restrict__ dst, const double *__restrict__ src, int64_t ld,
-                                           int rmax, int kmax, int tid, int unit) {
-    if (V2) {
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int e = tid + it * 256;
-            const int r = e >> 5, k = (e & 31) * 2;
-            double2 v = {0.0, 0.0};
-            if (r < rmax) {
-                const double *p = src + (int64_t)r * ld + k;
-                if (k + 1 < kmax)
-                    v = *reinterpret_cast<const double2 *>(p);
-                else if (k < kmax)
-                    v.x = *p;
-                if (unit != kNoUnit) {
-                    if (k < kmax) v.x = unit_lower(v.x, unit + r, k);
-                    if (k + 1 < kmax) v.y = unit_lower(v.y, unit + r, k + 1);
-                }
-            }
-            if (NEG) v = double2{-v.x, -v.y};
-            *reinterpret_cast<double2 *>(&dst[r * 64 + (k ^ ((r & 15) << 1))]) = v;
-        }
-    } else {
-#pragma unroll
-        for (int it = 0; it < 16; ++it) {
-            const int e = tid + it * 256;
-            const int r = e >> 6, k = e & 63;
-            double v = (r < rmax && k < kmax) ? src[(int64_t)r * ld + k] : 0.0;
-            if (unit != kNoUnit && r < rmax && k < kmax) v = unit_lower(v, unit + r, k);
-            dst[r * 64 + (k ^ ((r & 15) << 1))] = NEG ? -v : v;
-        }
-    }
-}
-
-template <bool V2>
-__device__ __forceinline__ void stage_kmajor(double *__restrict__ dst, const double *__restrict__ src, int64_t ld,
-                                             int kmax, int cmax, int tid, int unit) {
-    if (V2) {
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int e = tid + it * 256;
-            const int k = e >> 5, c = (e & 31) * 2;
-            double2 v = {0.0, 0.0};
-            if (k < kmax) {
-                const double *p = src + (int64_t)k * ld + c;
-                if (c + 1 < cmax)
-                    v = *reinterpret_cast<const double2 *>(p);
-                else if (c < cmax)
-                    v.x = *p;
-                if (unit != kNoUnit) {
-                    if (c < cmax) v.x = unit_lower(v.x, unit + k, c);
-                    if (c + 1 < cmax) v.y = unit_lower(v.y, unit + k, c + 1);
-                }
-            }
-            *reinterpret_cast<double2 *>(&dst[k * 64 + (c ^ ((k & 3) << 4))]) = v;
-        }
-    } else {
-#pragma unroll
-        for (int it = 0; it < 16; ++it) {
-            const int e = tid + it * 256;
-            const int k = e >> 6, c = e & 63;
-            double v = (k < kmax && c < cmax) ? src[(int64_t)k * ld + c] : 0.0;
-            if (unit != kNoUnit && k < kmax && c < cmax) v = unit_lower(v, unit + k, c);
-            dst[k * 64 + (c ^ ((k & 3) << 4))] = v;
-        }
-    }
-}
-
 // W_chunk (64 x 64 tile) = V^T C over the rows of one chunk. V: rows x jb at V
 // (the panel, its first 64 rows the diagonal block), C: rows x N. blockIdx.x is
 // the column tile, tile ntiles is V itself (V^T V for T), blockIdx.y the chunk.
 // Both operands are k-major as they lie in memory (k = the row), so nothing is
-// transposed on the way into LDS:
-//   A operand: lane l holds V[4 t + (l >> 4)][l & 15], B: C[4 t + (l >> 4)][l & 15],
-//   D: lane l, reg r holds W row (l >> 4) + 4 r, column l & 15 (the f64 map).
-// Every K step of 64 rows is staged and consumed between two barriers. The
-// tile is stored whole: past jb and past N it holds the zeros of the padding.
+// transposed on the way into LDS (dense_tile.hpp); the rows of V's diagonal
+// block are masked to unit lower on the way. Every K step of 64 rows is staged
+// and consumed between two barriers. The tile is stored whole: past jb and past
+// N it holds the zeros of the padding.
 template <bool V2>
 __global__ __launch_bounds__(256) void qr_vtc_kernel(const double *__restrict__ V, int64_t ldv, int jb,
                                                      const double *__restrict__ C, int64_t ldc, int N, int rows,
@@ -254,24 +165,13 @@ __global__ __launch_bounds__(256) void qr_vtc_kernel(const double *__restrict__ 
     for (int k0 = kb; k0 < ke; k0 += 64) {
         __syncthreads();  // the step before has been read
         const double *vk = V + (int64_t)k0 * ldv;
-        stage_kmajor<V2>(As, vk, ldv, rows - k0, jb, tid, k0);
+        stage_kmajor<V2, false>(As, vk, ldv, rows - k0, jb, tid, k0);
         if (tile < ntiles)
-            stage_kmajor<V2>(Bs, C + (int64_t)k0 * ldc + n0, ldc, rows - k0, N - n0, tid, kNoUnit);
+            stage_kmajor<V2, false>(Bs, C + (int64_t)k0 * ldc + n0, ldc, rows - k0, N - n0, tid);
         else
-            stage_kmajor<V2>(Bs, vk, ldv, rows - k0, jb, tid, k0);
+            stage_kmajor<V2, false>(Bs, vk, ldv, rows - k0, jb, tid, k0);
         __syncthreads();
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            const int k = 4 * t + g;
-            const double a0 = As[k * 64 + ((wr + l15) ^ (g << 4))];
-            const double a1 = As[k * 64 + ((wr + 16 + l15) ^ (g << 4))];
-            const double b0 = Bs[k * 64 + ((wc + l15) ^ (g << 4))];
-            const double b1 = Bs[k * 64 + ((wc + 16 + l15) ^ (g << 4))];
-            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-        }
+        tile_mma<kKMajor, kKMajor>(acc, As, Bs, 0, 64);
     }
     double *wt = W + (int64_t)chunk * 64 * ldw + n0;
 #pragma unroll
@@ -350,101 +250,6 @@ __global__ __launch_bounds__(256) void qr_z_kernel(const double *__restrict__ W,
     }
 }
 
-// C (M x N) -= A (M x K) B (K x N), K <= NB: lu_update_kernel's shape with
-// chol.hip's swizzle. A workgroup owns a 64 x 64 tile of C, stages -A (rows
-// layout) and B (k-major) once, each of its four waves takes a 32 x 32 quarter
-// as 2 x 2 MFMA tiles with C loaded into the accumulators.
-//   A operand: lane l holds A[l & 15][4 t + (l >> 4)], B: B[4 t + (l >> 4)][l & 15],
-//   C/D: lane l, reg r holds row (l >> 4) + 4 r, column l & 15.
-// UNIT: A is a panel's V, whose first block is masked to unit lower.
-template <bool V2, bool UNIT>
-__global__ __launch_bounds__(256) void qr_update_kernel(const double *__restrict__ A, int64_t lda,
-                                                        const double *__restrict__ B, int64_t ldb, double *C,
-                                                        int64_t ldc, int M, int N, int K) {
-    __shared__ __attribute__((aligned(16))) double As[NB * 64];
-    __shared__ __attribute__((aligned(16))) double Bs[NB * 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
-    stage_rows<V2, true>(As, A + (int64_t)m0 * lda, lda, M - m0, K, tid, UNIT ? m0 : kNoUnit);
-    stage_kmajor<V2>(Bs, B + n0, ldb, K, N - n0, tid, kNoUnit);
-    const int g = lane >> 4, l15 = lane & 15;
-    const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
-    f64x4 acc[2][2];
-#pragma unroll
-    for (int im = 0; im < 2; ++im)
-#pragma unroll
-        for (int in = 0; in < 2; ++in)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = m0 + wr + im * 16 + g + 4 * r, col = n0 + wc + in * 16 + l15;
-                acc[im][in][r] = (row < M && col < N) ? C[(int64_t)row * ldc + col] : 0.0;
-            }
-    __syncthreads();
-    for (int k0 = 0; k0 < K; k0 += 16) {  // uniform: a ragged block stops early
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int k = k0 + 4 * t + g;
-            const int kr = k ^ (l15 << 1);
-            const double a0 = As[(wr + l15) * 64 + kr], a1 = As[(wr + 16 + l15) * 64 + kr];
-            const double b0 = Bs[k * 64 + ((wc + l15) ^ (g << 4))], b1 = Bs[k * 64 + ((wc + 16 + l15) ^ (g << 4))];
-            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int im = 0; im < 2; ++im)
-#pragma unroll
-        for (int in = 0; in < 2; ++in)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = m0 + wr + im * 16 + g + 4 * r, col = n0 + wc + in * 16 + l15;
-                if (row < M && col < N) C[(int64_t)row * ldc + col] = acc[im][in][r];
-            }
-}
-
-// B (jb x ncols) <- R^-1 B by back substitution, R the upper jb x jb (jb <= NB)
-// block at t: a lane owns a column of B, R sits in LDS and is read as
-// broadcasts, k ascending, one division by the diagonal.
-__global__ __launch_bounds__(64) void qr_trsm_kernel(const double *__restrict__ t, int64_t ldt, int jb,
-                                                     double *__restrict__ b, int64_t ldb, int ncols) {
-    __shared__ double s[NB][NB];
-    __shared__ double xs[NB][64];
-    const int tid = threadIdx.x;
-    for (int e = tid; e < NB * NB; e += 64) {
-        const int i = e >> 6, k = e & 63;
-        if (i < jb && k < jb && k >= i) s[i][k] = t[(int64_t)i * ldt + k];
-    }
-    const int col = blockIdx.x * 64 + tid;
-    const bool ok = col < ncols;
-#pragma unroll 8
-    for (int i = 0; i < jb; ++i) xs[i][tid] = ok ? b[(int64_t)i * ldb + col] : 0.0;
-    __syncthreads();
-    for (int i = jb - 1; i >= 0; --i) {
-        double acc = xs[i][tid];
-#pragma unroll 4
-        for (int k = i + 1; k < jb; ++k) acc -= s[i][k] * xs[k][tid];
-        xs[i][tid] = acc / s[i][i];
-    }
-    if (!ok) return;
-#pragma unroll 8
-    for (int i = 0; i < jb; ++i) b[(int64_t)i * ldb + col] = xs[i][tid];
-}
-
-template <bool UNIT>
-int launch_update(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int M, int N,
-                  int K, hipStream_t s) {
-    if (M <= 0 || N <= 0 || K <= 0) return MPX_OK;
-    const dim3 grid((N + 63) / 64, (M + 63) / 64);
-    if (aligned16(A) && aligned16(B) && lda % 2 == 0 && ldb % 2 == 0)
-        hipLaunchKernelGGL((qr_update_kernel<true, UNIT>), grid, dim3(256), 0, s, A, lda, B, ldb, C, ldc, M, N, K);
-    else
-        hipLaunchKernelGGL((qr_update_kernel<false, UNIT>), grid, dim3(256), 0, s, A, lda, B, ldb, C, ldc, M, N, K);
-    MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
-    return MPX_OK;
-}
-
 int64_t round64(int64_t x) { return (x + 63) / 64 * 64; }
 int chunks_of(int rows) { return (rows + kChunkRows - 1) / kChunkRows; }
 
@@ -500,7 +305,7 @@ int block_apply(const double *v, int64_t ldv, int rows, int jb, const double *ta
             hipLaunchKernelGGL(qr_z_kernel<false>, dim3(ntiles), dim3(256), 0, s, ws.W, ldw, chunks, ws.T, ws.Z, ldz);
         MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
     }
-    if (mask & 8) return launch_update<true>(v, ldv, ws.Z, ldz, c, ldc, rows, N, jb, s);
+    if (mask & 8) return launch_dense_update<kRows, true>(v, ldv, ws.Z, ldz, c, ldc, rows, N, jb, s);
     return MPX_OK;
 }
 
@@ -561,7 +366,7 @@ extern "C" int mpx_qr_factor_f64(double *a, int m, int n, int64_t pitch, double 
     if (m == 0 || n == 0) return MPX_OK;
     hipStream_t s = as_stream(stream);
     const Ws ws = ws_of(workspace, m, n);
-    hipLaunchKernelGGL(qr_init_kernel, dim3(1), dim3(1), 0, s, info, ws.counter);
+    hipLaunchKernelGGL(dense_init_kernel<>, dim3(1), dim3(1), 0, s, info, ws.counter);
     MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
     for (int j0 = 0; j0 < n; j0 += NB)
         if (int rc = panel_step(a, m, n, pitch, tau, info, j0, 15, ws, s)) return rc;
@@ -575,7 +380,7 @@ extern "C" int mpx_qr_phase_f64(double *a, int m, int n, int64_t pitch, double *
     MPX_CHECK_ARG(phase >= 0 && phase < 4, "qr: phase outside 0..3");
     const Ws ws = ws_of(workspace, m, n);
     if (phase == 0 && j0 == 0) {
-        hipLaunchKernelGGL(qr_init_kernel, dim3(1), dim3(1), 0, as_stream(stream), info, ws.counter);
+        hipLaunchKernelGGL(dense_init_kernel<>, dim3(1), dim3(1), 0, as_stream(stream), info, ws.counter);
         MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
     }
     return panel_step(a, m, n, pitch, tau, info, j0, 1 << phase, ws, as_stream(stream));
@@ -615,10 +420,8 @@ extern "C" int mpx_qr_rsolve_f64(const double *qr, int n, int64_t pitch, double 
     for (int k0 = (n - 1) / NB * NB; k0 >= 0; k0 -= NB) {  // R x = y
         const int jb = n - k0 < NB ? n - k0 : NB;
         double *bk = b + (int64_t)k0 * pitch_b;
-        hipLaunchKernelGGL(qr_trsm_kernel, dim3((nrhs + 63) / 64), dim3(64), 0, s, qr + (int64_t)k0 * pitch + k0,
-                           pitch, jb, bk, pitch_b, nrhs);
-        MPX_RETURN_IF_HIP_ERROR(hipGetLastError());
-        if (int rc = launch_update<false>(qr + k0, pitch, bk, pitch_b, b, pitch_b, k0, nrhs, jb, s)) return rc;
+        if (int rc = launch_dense_trsm<true>(qr + (int64_t)k0 * pitch + k0, pitch, jb, bk, pitch_b, nrhs, s)) return rc;
+        if (int rc = launch_dense_update<kRows>(qr + k0, pitch, bk, pitch_b, b, pitch_b, k0, nrhs, jb, s)) return rc;
     }
     return MPX_OK;
 }

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Dense fp64 Householder QR on one MI355X (ops.qr_factor_): the time of the
 factorisation, its phases, the W = V^T C and C -= V Z kernels alone against
-their flop counts beside lu_update_kernel, the application of Q^T, least
+their flop counts beside the LU's update, the application of Q^T, least
 squares, and torch.geqrf, torch.ormqr and this package's LU (ops.lu_factor_, at
 the same n) in the same session.
 
@@ -23,7 +23,7 @@ overhead. ``phases_match_factor`` compares the results bit for bit.
 
 kernels: the first panel step's W and apply launches alone, median device time
 and rate: W is 2 (m)(64)(n - 64 + 64) flops (the V^T V tile included), apply
-2 (m)(64)(n - 64); ``lu_update`` is lu_update_kernel on the same trailing
+2 (m)(64)(n - 64); ``lu_update`` is the LU's update on the same trailing
 matrix (mpx_lu_phase_f64, phase 3; square shapes only), 2 (n - 64)^2 64 flops.
 
 apply_qt / lstsq: ops.qr_mul_q_(transpose=True) on 64 right-hand sides against
