@@ -71,6 +71,9 @@ C. Conventions against LAPACK (``np.linalg.qr(a, mode="raw")``) on the
 
 D. Plumbing: streams, CPU and GPU factors crossed, ``DenseQR``, empty shapes,
    every argument check.
+
+test_qr_exact.py goes on from here: exact families whose sums have many terms,
+m > 16384, the operand alignment classes and ``qr_solve_r_`` alone.
 """
 
 from __future__ import annotations
