@@ -28,7 +28,7 @@ ALIB      := $(B)/libmpx.a
 
 HIP_SRCS  := $(wildcard native/src/kernels/*.hip)
 HIP_OBJS  := $(patsubst native/src/kernels/%.hip,$(B)/k_%.o,$(HIP_SRCS))
-CORE_OBJS := $(B)/capi.o $(B)/comm.o $(B)/ipc.o
+CORE_OBJS := $(B)/capi.o $(B)/comm.o $(B)/ipc.o $(B)/classify_bounds.o
 CPU_OBJ   := $(B)/cpu_kernels.o
 LIB_OBJS  := $(HIP_OBJS) $(CORE_OBJS) $(CPU_OBJ)
 HDRS      := $(wildcard native/include/mpx/*.h native/include/mpx/*.hpp native/src/kernels/*.hpp native/src/cpu/*.h)
@@ -64,6 +64,10 @@ $(B)/capi.o: native/src/core/capi.cpp $(HDRS) | $(B)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(B)/ipc.o: native/src/core/ipc.cpp $(HDRS) | $(B)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# host only (no HIP header): the classifier's decision margins
+$(B)/classify_bounds.o: native/src/core/classify_bounds.cpp $(HDRS) | $(B)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # RCCL is not linked: comm.cpp binds the librccl torch already loaded (dlsym)

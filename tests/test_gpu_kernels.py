@@ -229,7 +229,7 @@ def test_classify_matches_cpu(gpu, nc, path):
     assert (t[..., 3] != cpu[..., 3]).float().mean() < 1e-3  # torch's summation order differs on near-ties
 
 
-@pytest.mark.parametrize("path", ["direct", "fast"])
+@pytest.mark.parametrize("path", ["direct", "fast", "mfma8", "mfma16"])
 @pytest.mark.parametrize("geom", [(1024, 1024), (4096, 64), (3, 32), (1, 1)])
 def test_classify_oversized_geometry(gpu, path, geom):
     """Caller grids far larger than the work: the empty workgroups are not
