@@ -4,6 +4,9 @@ They are the independent oracles of the numerics tests: fp32 for the image
 operators (luminance, Roberts, KxK conv via ``torch.nn.functional.conv2d``),
 fp64 for lab1/lab3/Jacobi. Summation order can differ from the native
 kernels', so image results agree to +-1 gray level except where stated.
+The conv's exact oracle is ``tests/conv_oracle.py``: numpy only, every fp32
+operation in the native order (one fma chain per filter), equal to the CPU
+reference and the GPU kernels byte for byte (``tests/test_conv_exact.py``).
 """
 
 from __future__ import annotations
